@@ -1,8 +1,14 @@
 """BASD distillation inner-loop benchmark (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--breakdown]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--full] [--dump-outputs DIR] [--breakdown]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds what takes time of its own
+or events inside the steps: the per-kernel roofline objects (HIP events around the selector's kernels in the timed
+steps) and the CPU-oracle baseline (tens of seconds on the host).  `--dump-outputs DIR` writes what the last timed step
+handed its caller as DIR/<name>.npy (see `dump_outputs`); the inputs are seeded, so two builds can be compared file by
+file.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the second form itself, as a
 child process, before this process has made any GPU call (a process that has touched the GPU is never re-exec'd).
@@ -207,6 +213,168 @@ def launch_check(args, rank: int, world: int) -> None:
         raise SystemExit(1)
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger output (4 MB in fp32)
+DUMP_LIMIT = 64 << 20          # bytes of all the files together
+
+
+def dump_outputs(out_dir: str, mod, loss, leaves: dict, logits, bucket) -> None:
+    """Write what the last timed step handed its caller as <out_dir>/<name>.npy (float32, float64 for the scalars):
+    the loss, the gradients of the logits and of every student token tensor, the selector temperatures' gradient and
+    the stand-in head's column means (both slices of the gradient bucket), and the subspace ranks.  An output of more
+    than DUMP_SAMPLE elements is written as `<name>_sample`: its elements at DUMP_SAMPLE flat indices drawn once by a
+    seeded CPU generator, in increasing order, so that every run of the same arguments picks the same ones."""
+    import numpy as np
+
+    sel = mod.layer_selector
+    n_col = len(mod.token_layers) * leaves[mod.token_layers[0]].shape[-1]
+    arrays = {"loss": loss.detach().double(), "logits_grad": logits.grad,
+              "log_temperatures_grad": sel.log_temperatures.grad, "head_column_means": bucket.student_view[:n_col],
+              "subspace_ranks": torch.tensor([float(r) for _, r in sorted(sel.subspace_ranks.items())],
+                                             dtype=torch.float64)}
+    for layer in mod.token_layers:
+        arrays[f"student_grad_layer{layer}"] = leaves[layer].grad
+    os.makedirs(out_dir, exist_ok=True)
+    total, picks = 0, {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            if n not in picks:
+                gen = torch.Generator().manual_seed(n)
+                picks[n] = torch.randperm(n, generator=gen)[:DUMP_SAMPLE].sort().values.to(t.device)
+            t, name = t[picks[n]], f"{name}_sample"
+        a = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_LIMIT >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def kernel_rooflines(args, shape: synth.LossShape, batch: int, mod, per_call: dict, marks) -> dict:
+    """--full: the roofline objects of the result line, from the HIP events recorded around the selector's launches
+    in the timed steps (`per_call`: entry point -> ms of each call; `marks`: the selector chain's timed events)."""
+    ab = algorithmic_bytes(shape, batch)
+    d_s, E, L = shape.d_s, shape.points, shape.layers_t
+    traffic = measured_traffic(args.config)
+    traffic_source = (f"{TRAFFIC_FILE}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier run of this "
+                      "command (2 x FETCH_SIZE + WRITE_SIZE, gfx950 correction), not collected in this run"
+                      if traffic else None)
+
+    def mean_ms(names):
+        """mean duration (ms) of the calls of these entry points, and calls per step"""
+        calls = [c for n in names for c in per_call.get(n, [])]
+        return (sum(calls) / len(calls), len(calls) / args.steps) if calls else (0.0, 0)
+
+    # --- dominant kernel by GPU time: the tridiagonalisation of the selector's Gram matrices
+    chain_step = bool(marks)
+    if ops.EIG_SOLVER == "tridiag":
+        if chain_step:
+            eig_ms, eig_calls = mean_ms(["basd_tridiag_ranked"])
+            n_mats = 2 * L if mod.chain_mode in (1, 2, 3) else 2 * L + E
+        else:
+            # kernel-by-kernel layout: every launch of the two entry points, all their matrices
+            eig_ms, eig_calls = mean_ms(["basd_tridiag", "basd_tridiag_ranked"])
+            n_mats = (2 * L + E) / max(eig_calls, 1)
+        packed = 256 < d_s <= 384
+        kernel_name = ("tridiag_packed_kernel (Householder tridiagonalisation, whole factorisation of one matrix in one "
+                       "CU's registers: upper triangle as packed row pairs; "
+                       + ("teacher-side launch, the one the host waits for)" if mod.chain_mode in (1, 2, 3) else
+                          "one launch over the teacher and student matrices)") if packed else
+                       "tridiag_kernel + tridiag_tail2_kernel (Householder tridiagonalisation of the selector's Gram "
+                       "matrices: shared stage + register-resident tail stage)")
+        note = ("latency-bound, neither an HBM stream nor MFMA work: n - 1 dependent Householder steps, each one pass over "
+                "the register-resident upper triangle + one wave's scalar chain + two workgroup barriers"
+                if packed else
+                "latency-bound, neither an HBM stream nor MFMA work: n - 1 dependent Householder steps (first stage: "
+                "matrix shared by several workgroups through L2; last 256 steps: matrix in one CU's registers)") + \
+               (".  `bound` is kept to the contract's vocabulary; the HBM fraction says how far from a stream this "
+                "kernel is by construction.  The roofline-bound kernels of the path are under roofline_mfma / "
+                "roofline_hbm_stream; the duration is the launch's span on its stream, inside the step")
+    else:
+        eig_ms, eig_calls = mean_ms(["basd_jacobi_onesided"])
+        n_mats = 2 * L + E
+        kernel_name = "jacobi_block_round_kernel (block one-sided Jacobi, symmetric eigen-solves of the selector)"
+        note = "latency-bound chain of dependent pair-steps, not an HBM stream (DESIGN.md section 5)"
+    launch_bytes = int(n_mats * 2 * d_s * d_s * 4)      # every matrix read once, its reflectors written once
+    achieved = launch_bytes / (eig_ms * 1e-3) / 1e9 if eig_ms > 0 else 0.0
+    # --- the MFMA-bound kernel: symmetric Gram launches (lower 128x128 tile pairs only).  The flops are those of the
+    # launches that are TIMED: the student launch (E matrices of order d_s over B n_s rows) in chain steps; in the
+    # kernel-by-kernel layout every syrk launch of the step -- student, and the teacher side's (2L Grams of the
+    # projected tokens, or L Grams in the teacher's own space where the teacher is about as wide as the student)
+    def pairs(n):
+        t = (n + 127) // 128
+        return t * (t + 1) // 2
+    student_flops = E * pairs(d_s) * 128 * 128 * 2.0 * batch * shape.n_s
+    syrk_ms, syrk_calls = mean_ms(["basd_syrk_multi"])
+    if chain_step:
+        syrk_flops = student_flops
+    else:
+        m_t = batch * shape.n_t
+        own_space = m_t >= d_s and shape.d_t <= 1.5 * d_s and mod.layer_selector.teacher_space_gram
+        teacher_flops = (L * pairs(shape.d_t) if own_space else 2 * L * pairs(d_s)) * 128 * 128 * 2.0 * m_t \
+            if m_t >= d_s else 0.0
+        syrk_flops = (student_flops + teacher_flops) / max(syrk_calls, 1)      # per launch, like syrk_ms
+    syrk_tf = syrk_flops / (syrk_ms * 1e-3) / 1e12 if syrk_ms > 0 else 0.0
+    # --- the HBM stream: column sums of the E student token tensors (every element read once, nothing written)
+    col_calls = [c for c in per_call.get("basd_colmean_multi", []) if c > 0]
+    if not chain_step and col_calls:
+        # the kernel-by-kernel layout times every launch of the entry point, in call order: the student layers' is
+        # the first of a step (then the teacher layers' where their Gram is formed in their own space, then the
+        # stand-in head's small one)
+        col_calls = col_calls[0::max(1, round(len(col_calls) / args.steps))]
+    col_ms = sum(col_calls) / len(col_calls) if col_calls else 0.0
+    col_bytes = ab["student"]
+    col_gbs = col_bytes / (col_ms * 1e-3) / 1e9 if col_ms > 0 else 0.0
+    return {
+        "roofline": {
+            "kernel": kernel_name,
+            "bound": "hbm", "regime": "latency", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic.get("tridiag"),
+            "traffic_source": traffic_source if traffic.get("tridiag") else None,
+            "launch_ms": eig_ms, "launches_per_step": eig_calls, "matrices_per_launch": n_mats,
+            "algorithmic_bytes_per_launch": launch_bytes,
+            "note": note,
+        },
+        "roofline_mfma": ({
+            # split operands: every fp32-grade multiply-add is SIX bf16 MFMA multiply-adds (hi hi, hi mid, mid hi, mid mid,
+            # hi lo, lo hi of the three-way exact bf16 split); `achieved` counts those, against the dense bf16 peak
+            "kernel": ("syrk_tn_split_kernel (+ syrk_reduce_kernel): centred Gram matrices of the E student layers" if marks else
+                       "syrk_tn_split_kernel (+ syrk_reduce_kernel): the step's symmetric Gram launches (student layers; teacher layers)"),
+            "bound": "mfma", "achieved": 6 * syrk_tf, "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s",
+            "frac": 6 * syrk_tf / MFMA_BF16_PEAK_TF, "traffic": traffic.get("syrk_tn_kernel"),
+            "traffic_source": traffic_source if traffic.get("syrk_tn_kernel") else None,
+            "launch_ms": syrk_ms, "launches_per_step": syrk_calls, "executed_flops_per_launch": 6 * syrk_flops,
+            "fp32_grade_tflops": syrk_tf, "fp32_mfma_peak_tflops": MFMA_F32_PEAK_TF,
+            "note": "bf16 MFMA (v_mfma_f32_32x32x16_bf16) on three-way split fp32 operands, fp32 accumulation: fp32-grade "
+                    "results at six bf16 multiply-adds each (fp32_grade_tflops = what an fp32 MFMA kernel would have to "
+                    "sustain, against its 157 TF peak); flops counted are the lower-triangular 128x128 tile pairs actually "
+                    "executed; timed inside the step, i.e. while the other streams' kernels share the chip",
+        } if _lib.query("basd_gemm_tuning_get") else {
+            "kernel": "syrk_tn_kernel (+ syrk_reduce_kernel): centred Gram matrices of the E student layers" if marks else
+                      "syrk_tn_kernel (+ syrk_reduce_kernel): the step's symmetric Gram launches (student layers; teacher layers)",
+            "bound": "mfma", "achieved": syrk_tf, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
+            "frac": syrk_tf / MFMA_F32_PEAK_TF, "traffic": traffic.get("syrk_tn_kernel"),
+            "traffic_source": traffic_source if traffic.get("syrk_tn_kernel") else None,
+            "launch_ms": syrk_ms, "launches_per_step": syrk_calls, "executed_flops_per_launch": syrk_flops,
+            "note": "fp32 MFMA (v_mfma_f32_32x32x2_f32); flops counted are the lower-triangular 128x128 tile "
+                    "pairs actually executed; timed inside the step, i.e. while the other streams' kernels "
+                    "share the chip",
+        }),
+        "roofline_hbm_stream": {
+            "kernel": "colsum_partial_vec_kernel (+ colsum_final_kernel): column means of the E student layers",
+            "bound": "hbm", "achieved": col_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": col_gbs / HBM_PEAK_GBS, "traffic": traffic.get("colsum_partial_vec_kernel"),
+            "traffic_source": traffic_source if traffic.get("colsum_partial_vec_kernel") else None,
+            "launch_ms": col_ms, "launch_ms_min_max": [min(col_calls), max(col_calls)] if col_calls else None,
+            "launches_per_step": len(col_calls) / args.steps,
+            "algorithmic_bytes_per_launch": col_bytes,
+            "note": "every element of E (B, N, D) token tensors read once, nothing written back; the selector's launch "
+                    "over the strided CLS-sliced views, inside the step (beside the teacher side's factorisation and "
+                    "the Procrustes kernels of the caller's stream)",
+        },
+    }
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -216,7 +384,11 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the config's)")
     ap.add_argument("--contiguous", action="store_true", help="contiguous inputs instead of the callers' strided views")
     ap.add_argument("--breakdown", action="store_true", help="print a per-entry-point time table to stderr")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline objects (per-kernel events in the timed steps) and the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU-oracle baseline")
     ap.add_argument("--cpu-sample-batch", type=int, default=32)
     ap.add_argument("--cpu-repeats", type=int, default=3)
     ap.add_argument("--cpu-baseline-only", action="store_true",
@@ -228,6 +400,8 @@ def main() -> None:
     ap.add_argument("--launch-check", action="store_true",
                     help="CPU rehearsal of the N > 1 launch: gloo group + one all-reduce of the gradient bucket, no GPU call")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_workers(args.gpus, sys.argv[1:]))
@@ -298,17 +472,19 @@ def main() -> None:
     gc.freeze()
     mod.layer_selector.finish_pending()       # deferred selector tail of the last warm-up step: outside the timing
     bucket.wait(all_slots=True)
-    # Kernels reported with a roofline object, timed live with HIP events recorded on the stream they are queued on
-    # (each of these entry points is one kernel, plus a small fold for the Gram):
-    #   basd_tridiag_ranked / basd_tridiag   Householder tridiagonalisation (two kernels: shared stage + tail stage)
-    #   basd_syrk_multi                      symmetric Gram matrices on the fp32 MFMA
-    #   basd_colmean_multi                   column sums: the purest HBM stream of the step
-    timed = {"basd_tridiag", "basd_tridiag_ranked", "basd_syrk_multi", "basd_colmean_multi", "basd_jacobi_onesided"}
-    _lib.timing = {}
-    _lib.timed_names = None if args.breakdown else timed
-    # single-teacher steps queue the selector inside ONE library call (basd_selector_chain): there the same launches are
-    # bracketed by timed events the call records itself, on the stream each launch is queued on
-    chain.TIMING = []
+    kernel_timing = args.full or args.breakdown
+    if kernel_timing:
+        # Kernels reported with a roofline object, timed live with HIP events recorded on the stream they are queued on
+        # (each of these entry points is one kernel, plus a small fold for the Gram):
+        #   basd_tridiag_ranked / basd_tridiag   Householder tridiagonalisation (two kernels: shared stage + tail stage)
+        #   basd_syrk_multi                      symmetric Gram matrices on the fp32 MFMA
+        #   basd_colmean_multi                   column sums: the purest HBM stream of the step
+        timed = {"basd_tridiag", "basd_tridiag_ranked", "basd_syrk_multi", "basd_colmean_multi", "basd_jacobi_onesided"}
+        _lib.timing = {}
+        _lib.timed_names = None if args.breakdown else timed
+        # single-teacher steps queue the selector inside ONE library call (basd_selector_chain): there the same launches
+        # are bracketed by timed events the call records itself, on the stream each launch is queued on
+        chain.TIMING = []
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -330,106 +506,39 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, ms_min, ms_max = float(t[0].item()), 1e3 * float(-t[1].item()) / args.steps, 1e3 * float(t[0].item()) / args.steps
 
-    per_call = {k: [a.elapsed_time(b) for a, b in v] for k, v in timing.items()}      # ms
+    if kernel_timing:
+        per_call = {k: [a.elapsed_time(b) for a, b in v] for k, v in timing.items()}      # ms
 
-    def span(a: str, b: str) -> list:
-        """per-step duration (ms) between two marks of the selector chain"""
-        out = []
-        for m in marks:
-            try:
-                out.append(1e-3 * chain.elapsed_us(m[a], m[b]))
-            except (KeyError, RuntimeError):
-                pass
-        return out
-    if marks:
-        # same names as the entry points the kernel-by-kernel layout times; the factorisation the host waits for is the
-        # teacher side's (its span contains the wait for a free CU and the rank kernel: what the step pays)
-        per_call["basd_tridiag_ranked"] = span("tm_tri0", "ranks")
-        per_call["basd_syrk_multi"] = span("tm_scol1", "tm_sgram")
-        per_call["basd_colmean_multi"] = span("tm_scol0", "tm_scol1")      # (not the stand-in head's small launch)
-    if args.breakdown and rank == 0:
-        tot = sum(sum(v) for v in per_call.values())
-        print(f"{'entry point':32s} {'calls/step':>10s} {'ms/step':>9s} {'share':>6s}", file=sys.stderr)
-        for k, v in sorted(per_call.items(), key=lambda kv: -sum(kv[1])):
-            print(f"{k:32s} {len(v) / args.steps:10.1f} {sum(v) / args.steps:9.3f} {100 * sum(v) / tot:5.1f}%",
+        def span(a: str, b: str) -> list:
+            """per-step duration (ms) between two marks of the selector chain"""
+            out = []
+            for m in marks:
+                try:
+                    out.append(1e-3 * chain.elapsed_us(m[a], m[b]))
+                except (KeyError, RuntimeError):
+                    pass
+            return out
+        if marks:
+            # same names as the entry points the kernel-by-kernel layout times; the factorisation the host waits for is the
+            # teacher side's (its span contains the wait for a free CU and the rank kernel: what the step pays)
+            per_call["basd_tridiag_ranked"] = span("tm_tri0", "ranks")
+            per_call["basd_syrk_multi"] = span("tm_scol1", "tm_sgram")
+            per_call["basd_colmean_multi"] = span("tm_scol0", "tm_scol1")      # (not the stand-in head's small launch)
+        if args.breakdown and rank == 0:
+            tot = sum(sum(v) for v in per_call.values())
+            print(f"{'entry point':32s} {'calls/step':>10s} {'ms/step':>9s} {'share':>6s}", file=sys.stderr)
+            for k, v in sorted(per_call.items(), key=lambda kv: -sum(kv[1])):
+                print(f"{k:32s} {len(v) / args.steps:10.1f} {sum(v) / args.steps:9.3f} {100 * sum(v) / tot:5.1f}%",
+                      file=sys.stderr)
+            print(f"{'sum of kernel spans':32s} {'':10s} {tot / args.steps:9.3f}   (wall {1e3 * elapsed / args.steps:.3f} ms/step)",
                   file=sys.stderr)
-        print(f"{'sum of kernel spans':32s} {'':10s} {tot / args.steps:9.3f}   (wall {1e3 * elapsed / args.steps:.3f} ms/step)",
-              file=sys.stderr)
 
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
         ab = algorithmic_bytes(shape, batch)
         d_s, E, L = shape.d_s, shape.points, shape.layers_t
-        traffic = measured_traffic(args.config)
-        traffic_source = (f"{TRAFFIC_FILE}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier run of this "
-                          "command (2 x FETCH_SIZE + WRITE_SIZE, gfx950 correction), not collected in this run"
-                          if traffic else None)
-
-        def mean_ms(names):
-            """mean duration (ms) of the calls of these entry points, and calls per step"""
-            calls = [c for n in names for c in per_call.get(n, [])]
-            return (sum(calls) / len(calls), len(calls) / args.steps) if calls else (0.0, 0)
-
-        # --- dominant kernel by GPU time: the tridiagonalisation of the selector's Gram matrices
-        chain_step = bool(marks)
-        if ops.EIG_SOLVER == "tridiag":
-            if chain_step:
-                eig_ms, eig_calls = mean_ms(["basd_tridiag_ranked"])
-                n_mats = 2 * L if mod.chain_mode in (1, 2, 3) else 2 * L + E
-            else:
-                # kernel-by-kernel layout: every launch of the two entry points, all their matrices
-                eig_ms, eig_calls = mean_ms(["basd_tridiag", "basd_tridiag_ranked"])
-                n_mats = (2 * L + E) / max(eig_calls, 1)
-            packed = 256 < d_s <= 384
-            kernel_name = ("tridiag_packed_kernel (Householder tridiagonalisation, whole factorisation of one matrix in one "
-                           "CU's registers: upper triangle as packed row pairs; "
-                           + ("teacher-side launch, the one the host waits for)" if mod.chain_mode in (1, 2, 3) else
-                              "one launch over the teacher and student matrices)") if packed else
-                           "tridiag_kernel + tridiag_tail2_kernel (Householder tridiagonalisation of the selector's Gram "
-                           "matrices: shared stage + register-resident tail stage)")
-            note = ("latency-bound, neither an HBM stream nor MFMA work: n - 1 dependent Householder steps, each one pass over "
-                    "the register-resident upper triangle + one wave's scalar chain + two workgroup barriers"
-                    if packed else
-                    "latency-bound, neither an HBM stream nor MFMA work: n - 1 dependent Householder steps (first stage: "
-                    "matrix shared by several workgroups through L2; last 256 steps: matrix in one CU's registers)") + \
-                   (".  `bound` is kept to the contract's vocabulary; the HBM fraction says how far from a stream this "
-                    "kernel is by construction.  The roofline-bound kernels of the path are under roofline_mfma / "
-                    "roofline_hbm_stream; the duration is the launch's span on its stream, inside the step")
-        else:
-            eig_ms, eig_calls = mean_ms(["basd_jacobi_onesided"])
-            n_mats = 2 * L + E
-            kernel_name = "jacobi_block_round_kernel (block one-sided Jacobi, symmetric eigen-solves of the selector)"
-            note = "latency-bound chain of dependent pair-steps, not an HBM stream (DESIGN.md section 5)"
-        launch_bytes = int(n_mats * 2 * d_s * d_s * 4)      # every matrix read once, its reflectors written once
-        achieved = launch_bytes / (eig_ms * 1e-3) / 1e9 if eig_ms > 0 else 0.0
-        # --- the MFMA-bound kernel: symmetric Gram launches (lower 128x128 tile pairs only).  The flops are those of the
-        # launches that are TIMED: the student launch (E matrices of order d_s over B n_s rows) in chain steps; in the
-        # kernel-by-kernel layout every syrk launch of the step -- student, and the teacher side's (2L Grams of the
-        # projected tokens, or L Grams in the teacher's own space where the teacher is about as wide as the student)
-        def pairs(n):
-            t = (n + 127) // 128
-            return t * (t + 1) // 2
-        student_flops = E * pairs(d_s) * 128 * 128 * 2.0 * batch * shape.n_s
-        syrk_ms, syrk_calls = mean_ms(["basd_syrk_multi"])
-        if chain_step:
-            syrk_flops = student_flops
-        else:
-            m_t = batch * shape.n_t
-            own_space = m_t >= d_s and shape.d_t <= 1.5 * d_s and mod.layer_selector.teacher_space_gram
-            teacher_flops = (L * pairs(shape.d_t) if own_space else 2 * L * pairs(d_s)) * 128 * 128 * 2.0 * m_t \
-                if m_t >= d_s else 0.0
-            syrk_flops = (student_flops + teacher_flops) / max(syrk_calls, 1)      # per launch, like syrk_ms
-        syrk_tf = syrk_flops / (syrk_ms * 1e-3) / 1e12 if syrk_ms > 0 else 0.0
-        # --- the HBM stream: column sums of the E student token tensors (every element read once, nothing written)
-        col_calls = [c for c in per_call.get("basd_colmean_multi", []) if c > 0]
-        if not chain_step and col_calls:
-            # the kernel-by-kernel layout times every launch of the entry point, in call order: the student layers' is
-            # the first of a step (then the teacher layers' where their Gram is formed in their own space, then the
-            # stand-in head's small one)
-            col_calls = col_calls[0::max(1, round(len(col_calls) / args.steps))]
-        col_ms = sum(col_calls) / len(col_calls) if col_calls else 0.0
-        col_bytes = ab["student"]
-        col_gbs = col_bytes / (col_ms * 1e-3) / 1e9 if col_ms > 0 else 0.0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, mod, loss, leaves, logits, bucket)
         line = {
             "metric": "distillation images/sec (BASD loss fwd+bwd+grad all-reduce), DeiT-S<-ResNet-50 @ bs256/GPU"
             if args.config == "cfg2" else f"distillation images/sec (BASD loss fwd+bwd+grad all-reduce), {shape.name}",
@@ -460,7 +569,7 @@ def main() -> None:
                 "grad_allreduce": "RCCL all-reduce (mean) per step on the communicator's stream" if world > 1
                 else "none at world size 1 (bucket packed, nothing to exchange)",
                 "rank_readback": mod.rank_readback, "readback_deferred_steps": mod.readback_deferred_steps,
-                "selector": (f"basd_selector_chain mode {mod.chain_mode}" if marks else "kernel by kernel"),
+                "selector": (f"basd_selector_chain mode {mod.chain_mode}" if mod._chain_plans else "kernel by kernel"),
                 "parallelism": f"dp{world}",
             },
             "path_hbm": {
@@ -468,56 +577,12 @@ def main() -> None:
                 "achieved_GBps": ab["step"] / (ms_step * 1e-3) / 1e9,
                 "frac_of_8TBps": ab["step"] / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
             },
-            "roofline": {
-                "kernel": kernel_name,
-                "bound": "hbm", "regime": "latency", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic.get("tridiag"),
-                "traffic_source": traffic_source if traffic.get("tridiag") else None,
-                "launch_ms": eig_ms, "launches_per_step": eig_calls, "matrices_per_launch": n_mats,
-                "algorithmic_bytes_per_launch": launch_bytes,
-                "note": note,
-            },
-            "roofline_mfma": ({
-                # split operands: every fp32-grade multiply-add is SIX bf16 MFMA multiply-adds (hi hi, hi mid, mid hi, mid mid,
-                # hi lo, lo hi of the three-way exact bf16 split); `achieved` counts those, against the dense bf16 peak
-                "kernel": ("syrk_tn_split_kernel (+ syrk_reduce_kernel): centred Gram matrices of the E student layers" if marks else
-                           "syrk_tn_split_kernel (+ syrk_reduce_kernel): the step's symmetric Gram launches (student layers; teacher layers)"),
-                "bound": "mfma", "achieved": 6 * syrk_tf, "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s",
-                "frac": 6 * syrk_tf / MFMA_BF16_PEAK_TF, "traffic": traffic.get("syrk_tn_kernel"),
-                "traffic_source": traffic_source if traffic.get("syrk_tn_kernel") else None,
-                "launch_ms": syrk_ms, "launches_per_step": syrk_calls, "executed_flops_per_launch": 6 * syrk_flops,
-                "fp32_grade_tflops": syrk_tf, "fp32_mfma_peak_tflops": MFMA_F32_PEAK_TF,
-                "note": "bf16 MFMA (v_mfma_f32_32x32x16_bf16) on three-way split fp32 operands, fp32 accumulation: fp32-grade "
-                        "results at six bf16 multiply-adds each (fp32_grade_tflops = what an fp32 MFMA kernel would have to "
-                        "sustain, against its 157 TF peak); flops counted are the lower-triangular 128x128 tile pairs actually "
-                        "executed; timed inside the step, i.e. while the other streams' kernels share the chip",
-            } if _lib.query("basd_gemm_tuning_get") else {
-                "kernel": "syrk_tn_kernel (+ syrk_reduce_kernel): centred Gram matrices of the E student layers" if marks else
-                          "syrk_tn_kernel (+ syrk_reduce_kernel): the step's symmetric Gram launches (student layers; teacher layers)",
-                "bound": "mfma", "achieved": syrk_tf, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
-                "frac": syrk_tf / MFMA_F32_PEAK_TF, "traffic": traffic.get("syrk_tn_kernel"),
-                "traffic_source": traffic_source if traffic.get("syrk_tn_kernel") else None,
-                "launch_ms": syrk_ms, "launches_per_step": syrk_calls, "executed_flops_per_launch": syrk_flops,
-                "note": "fp32 MFMA (v_mfma_f32_32x32x2_f32); flops counted are the lower-triangular 128x128 tile "
-                        "pairs actually executed; timed inside the step, i.e. while the other streams' kernels "
-                        "share the chip",
-            }),
-            "roofline_hbm_stream": {
-                "kernel": "colsum_partial_vec_kernel (+ colsum_final_kernel): column means of the E student layers",
-                "bound": "hbm", "achieved": col_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": col_gbs / HBM_PEAK_GBS, "traffic": traffic.get("colsum_partial_vec_kernel"),
-                "traffic_source": traffic_source if traffic.get("colsum_partial_vec_kernel") else None,
-                "launch_ms": col_ms, "launch_ms_min_max": [min(col_calls), max(col_calls)] if col_calls else None,
-                "launches_per_step": len(col_calls) / args.steps,
-                "algorithmic_bytes_per_launch": col_bytes,
-                "note": "every element of E (B, N, D) token tensors read once, nothing written back; the selector's launch "
-                        "over the strided CLS-sliced views, inside the step (beside the teacher side's factorisation and "
-                        "the Procrustes kernels of the caller's stream)",
-            },
         }
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(args.config, shape, min(args.cpu_sample_batch, batch),
-                                                repeats=args.cpu_repeats)
+        if args.full:
+            line.update(kernel_rooflines(args, shape, batch, mod, per_call, marks))
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(args.config, shape, min(args.cpu_sample_batch, batch),
+                                                    repeats=args.cpu_repeats)
         print(json.dumps(line))
     if use_comm:
         dist.destroy_process_group()

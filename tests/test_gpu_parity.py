@@ -171,15 +171,14 @@ def test_full_small_golden(golden, tag):
                                   g[f"{tag}_grad_log_temperatures"])
 
 
-@pytest.mark.parametrize("tag", ["vit", "vit_same"])
-def test_full_small_golden_multilayer(golden, tag):
-    """Multi-layer (ViT) teachers: ranks, distances, mixing weights, loss value and the gradients that flow
-    through the selector (route (b): principal angles -> eigenvectors of the student Gram) and the mixing
-    weights (teacher tokens + attention) -- looser tolerance there, the route is ill-conditioned
-    (SURVEY.md section 7, hard part 3)."""
+def _full_small_golden_multilayer(golden, tag, small_student_jacobi):
     g = golden("full_small.npz")
     shape, seed = S.SMALL[tag]
     mod = _module(shape, 0.01)
+    mod.layer_selector.small_student_jacobi = small_student_jacobi
+    adjoint = mod.layer_selector._eigvec_adjoint_leading
+    leading_k_calls = []
+    mod.layer_selector._eigvec_adjoint_leading = lambda *a: leading_k_calls.append(1) or adjoint(*a)
     inp = synth.make_inputs(shape, seed, device=DEV)
     leaves = {k: v.requires_grad_(True) for k, v in inp.student.items()}
     logits = inp.logits.requires_grad_(True)
@@ -188,6 +187,8 @@ def test_full_small_golden_multilayer(golden, tag):
     np.testing.assert_allclose(mod.last_components["mix"].cpu().numpy(), g[f"{tag}_mix_weights"], rtol=2e-3, atol=1e-6)
     np.testing.assert_allclose(loss.item(), g[f"{tag}_loss"], rtol=1e-4)
     loss.backward()
+    # which student-eigenvector backward ran: the leading-k adjoint (shifted solves) or the full Jacobi eigenvectors
+    assert bool(leading_k_calls) == (not small_student_jacobi)
     np.testing.assert_allclose(logits.grad.cpu().numpy(), g[f"{tag}_grad_logits"], rtol=1e-4, atol=1e-8)
     for l in mod.token_layers:
         ref = g[f"{tag}_grad_student_{l}"]
@@ -197,6 +198,23 @@ def test_full_small_golden_multilayer(golden, tag):
     gt = mod.layer_selector.log_temperatures.grad.cpu().numpy()
     print(tag, "dlogtau", gt, g[f"{tag}_grad_log_temperatures"])
     np.testing.assert_allclose(gt, g[f"{tag}_grad_log_temperatures"], rtol=2e-3, atol=1e-7)
+
+
+@pytest.mark.parametrize("tag", ["vit", "vit_same"])
+def test_full_small_golden_multilayer(golden, tag):
+    """Multi-layer (ViT) teachers: ranks, distances, mixing weights, loss value and the gradients that flow
+    through the selector (route (b): principal angles -> eigenvectors of the student Gram) and the mixing
+    weights (teacher tokens + attention) -- looser tolerance there, the route is ill-conditioned
+    (SURVEY.md section 7, hard part 3)."""
+    _full_small_golden_multilayer(golden, tag, True)
+
+
+@pytest.mark.parametrize("tag", ["vit", "vit_same"])
+def test_full_small_golden_multilayer_tridiagonal_backward(golden, tag):
+    """The same against the goldens on the tridiagonal route's backward (leading-k eigenvectors + shifted solves):
+    the route of student orders past the LDS-resident Jacobi solver (cfg-4's 768), which the toy shapes otherwise
+    leave to the Jacobi eigenvectors."""
+    _full_small_golden_multilayer(golden, tag, False)
 
 
 @pytest.mark.parametrize("name,seed,batch,ls,strided", [

@@ -18,9 +18,9 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python3 tools/pmc_traffic.py $OUT/cfg2_FETCH_SIZE.csv $OUT/cfg2_WRITE_SIZE.csv cfg2 $OUT/r03_traffic.json
 # un-profiled bench lines (the numbers to quote); cfg2 with the CPU baseline leg
-python3 bench.py > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
-for cfg in cfg1 cfg5 cfg4; do python3 bench.py --config $cfg --no-cpu-baseline > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err; done
-python3 bench.py --teacher-rank 160 --no-cpu-baseline > $OUT/bench_cfg2_rank160.json 2> $OUT/bench_cfg2_rank160.err
+python3 bench.py --full > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+for cfg in cfg1 cfg5 cfg4; do python3 bench.py --full --config $cfg --no-cpu-baseline > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err; done
+python3 bench.py --full --teacher-rank 160 --no-cpu-baseline > $OUT/bench_cfg2_rank160.json 2> $OUT/bench_cfg2_rank160.err
 for cfg in cfg2 cfg1 cfg5 cfg4 cfg2_rank160; do python3 -c "import json;d=json.load(open('$OUT/bench_$cfg.json'));print('$cfg', round(d['ms_per_step'],3),'ms/step', round(d['value'],1),'img/s loss',d['loss'], {k: round(d[k]['frac'],4) for k in ('roofline','roofline_mfma','roofline_hbm_stream')})"; done
 python3 tools/step_clock.py cfg2 > $OUT/step_clock_cfg2.txt 2>&1
 BASD_TRIDIAG_CLOCKS=1 python3 tools/step_clock.py cfg2 2>&1 | grep -i "factorisation kernel" > $OUT/packed_kernel_in_step.txt

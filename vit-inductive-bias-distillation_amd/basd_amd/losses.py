@@ -456,6 +456,9 @@ class GrassmannianLayerSelector(nn.Module):
         self.rank1_mp = os.environ.get("BASD_RANK1_MP", "1") != "0"
         self.merge_factorisations = os.environ.get("BASD_MERGE_FACTORISATIONS", "1") != "0"   # cfg-4: 46.4 -> ? ms
         self.overlap_student_side = os.environ.get("BASD_OVERLAP_STUDENT_SIDE", "0") != "0"    # measured: 63.7 vs 58.3 ms at cfg-4
+        # backward of multi-layer teachers at student orders the LDS-resident Jacobi solver takes: full Jacobi eigenvectors
+        # (see ``_spectra_async``); False keeps the tridiagonal route of larger students (tests cover it at small shapes)
+        self.small_student_jacobi = True
         self._student_streams: dict = {}
 
         # Same global-RNG consumption order as the reference (proj_s, then proj_t), on CPU.
@@ -609,8 +612,16 @@ class GrassmannianLayerSelector(nn.Module):
         dev = students[0].device
         tri = ops.EIG_SOLVER == "tridiag"
         # all student eigenvectors are only needed by the Jacobi-mode backward; the tridiagonal route's backward
-        # works from the leading k and shifted solves (``_distance_backward``)
-        stud_jacobi = not tri
+        # works from the leading k and shifted solves (``_distance_backward``).  A backward at student orders whose
+        # Gram fits the LDS-resident Jacobi solver takes the Jacobi route even so (``small_student_jacobi``): where the
+        # leading eigenvalues cluster (noise directions inside the teacher rank) the shifted solves lose about 1e-3 of
+        # the student gradient and the full eigenvectors do not (d_s = 64, 576 tokens, layer 0: 1.8e-3 from an fp64
+        # evaluation and 2.04e-3 from the fp32 oracle on the tridiagonal route, 3.4e-4 from fp64 on this one), and at
+        # those orders the solve is one small launch.  Measured cost per fwd+bwd step: 2.31 -> 2.56 ms (toy ViT teacher,
+        # d_s 96), 20.9 -> 21.3 (d_s 64, 576 tokens), 14.7 -> 16.6 (d_s 192, 12 teacher layers, B 128).  Larger
+        # students (cfg-4's 768) keep the tridiagonal route.
+        stud_jacobi = not tri or (all_student_vectors and self.small_student_jacobi
+                                  and bool(ops._lib.query("basd_jacobi_lds_square_fits", d_s)))
         st = dict(E=E, L=L, tri=tri, stud_jacobi=stud_jacobi, student_stream=student_stream)
 
         cur = torch.cuda.current_stream()
@@ -659,7 +670,7 @@ class GrassmannianLayerSelector(nn.Module):
         # queued BEHIND the teacher chain and gated on an event recorded after that stage -- from there on the teacher
         # factorisation sits in one CU per matrix and no longer cares.
         gated = student_stream is not None and tri and self.gate_student_chain and gate_student
-        if (tri and self.rank1_mp and self.merge_factorisations and student_stream is None
+        if (tri and not stud_jacobi and self.rank1_mp and self.merge_factorisations and student_stream is None
                 and self._teacher_space_route(teachers)):
             # ONE factorisation launch over the L centred teacher Grams and the E student Grams (multi-layer ViT teachers:
             # a launch over E = 4 matrices of order 768 takes 2.8 ms, over L = 24 5.0 -- both are bound by dependent
