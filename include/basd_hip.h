@@ -13,7 +13,7 @@
  *   - dtype codes: 0 = fp32, 1 = bf16 (inputs only; all arithmetic and outputs are fp32/fp64);
  *   - entry points are re-entrant and keep no global mutable state, with a few process-wide test / tuning hooks as the
  *     only exceptions: basd_tridiag_tuning, basd_jacobi_tuning, basd_jacobi_ordering, basd_gemm_tuning, basd_procrustes_tuning (none is called by the
- *     loss).
+ *     loss), and the launch counter behind basd_sfadamw_launches (diagnostics).
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -617,6 +617,52 @@ int basd_resample_tokens(const void* x, int dtype, long sb, long sn, long sd, in
 int basd_resample_tokens_adjoint(const float* dy, int B, int n_in, int n_out, int D, const int* tap0,
                                  const int* tap1, const float* lam, const int* range0, const int* range1, float* dx,
                                  hipStream_t stream);
+
+/* ---- the optimizer: schedule-free AdamW over all parameters in one launch ---------------------------- */
+
+/* One row per parameter tensor (device table).  y: the parameter itself (fp32, the `y` sequence in train mode);
+ * z, v: the optimizer's state (`z`, `exp_avg_sq`); grad: NULL = no gradient this step, the tensor is skipped;
+ * group: index into the per-group scalars.  Any pointer may be only 4-byte aligned (16-byte accesses are used
+ * where y, z, v -- and, separately, grad -- allow them). */
+typedef struct BasdSfAdamwTensor {
+    float* y;
+    float* z;
+    float* v;
+    float* grad;
+    long numel;
+    long group;
+} BasdSfAdamwTensor;
+
+/* Host-computed scalars of one parameter group for one step (HOST memory; they reach the kernel by value). */
+typedef struct BasdSfAdamwGroup {
+    double lr;                 /* group lr x warm-up factor (`scheduled_lr`) */
+    double ckp1;               /* weight / weight_sum */
+    double bias_correction2;   /* 1 - beta2^(k+1) */
+    double beta1, beta2, eps, weight_decay;
+} BasdSfAdamwGroup;
+
+#define BASD_SFADAMW_MAX_GROUPS 8
+
+/* Elements per chunk of the chunk lists below. */
+int basd_sfadamw_chunk(void);
+
+/* replaces: `self.optimizer.step()` + `self.optimizer.zero_grad()`  src/training/trainer.py:158-159 with the
+ * `AdamWScheduleFree` of trainer.py:54-58 (incl. the second parameter group of :74-76).  Per element
+ *   g = grad * grad_scale;  v = beta2 v + (1 - beta2) g g;  gn = g / (sqrt(v / bias_correction2) + eps) + weight_decay y;
+ *   y = y + ckp1 (z - y);  y = y + lr (beta1 (1 - ckp1) - 1) gn;  z = z - lr gn;  grad = 0 if zero_grad.
+ * chunks: n_chunks pairs (row of `table`, chunk index inside that tensor) on the device, covering every tensor.
+ * groups: n_groups <= BASD_SFADAMW_MAX_GROUPS entries on the HOST.  ONE launch; n_chunks == 0 launches nothing. */
+int basd_sfadamw_step(const BasdSfAdamwTensor* table, const int* chunks, int n_chunks, const BasdSfAdamwGroup* groups,
+                      int n_groups, float grad_scale, int zero_grad, hipStream_t stream);
+
+/* replaces: `self.optimizer.train()` / `self.optimizer.eval()`  src/training/trainer.py:180,:184:
+ * y <- y + weights[group] (z - y) for every tensor of the table, ONE launch (grad is not read).
+ * weights: n_groups <= BASD_SFADAMW_MAX_GROUPS floats on the HOST. */
+int basd_sfadamw_swap(const BasdSfAdamwTensor* table, const int* chunks, int n_chunks, const float* weights,
+                      int n_groups, hipStream_t stream);
+
+/* diagnostics: kernel launches made by the two entry points above since the library was loaded (process-wide). */
+long basd_sfadamw_launches(void);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ Sub-modules:
                HIP library is missing -- there is no CPU fallback)
   ``ops``      torch.autograd Functions / host orchestration over the C-ABI
   ``losses``   ``BASDLoss`` / ``GrassmannianLayerSelector`` / free functions
+  ``optim``    ``AdamWScheduleFree``: the reference trainer's optimizer, one launch per step
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
 __version__ = "0.1.0"

@@ -109,6 +109,10 @@ SIGNATURES = {
     "basd_stream_create_priority": [vp, i32],
     "basd_event_create_timed": [vp],
     "basd_event_elapsed_ms": [vp, vp, vp],
+    "basd_sfadamw_chunk": [],
+    "basd_sfadamw_step": [vp, vp, i32, vp, i32, f32, i32, vp],
+    "basd_sfadamw_swap": [vp, vp, i32, vp, i32, vp],
+    "basd_sfadamw_launches": [],
 }
 
 class ProcrustesArgs(C.Structure):
@@ -157,7 +161,7 @@ EINVAL, EUNSUPPORTED = -1, -2        # BASD_EINVAL / BASD_EUNSUPPORTED of includ
 # sizing helpers declared `long` in include/basd_hip.h
 LONG_RESULTS = {"basd_tridiag_workspace_bytes", "basd_jacobi_twopass_workspace_bytes",
                 "basd_mix_grad_tokens_scratch_floats", "basd_teacher_center_stream_scratch_floats",
-                "basd_rank_certificate_scratch_bytes"}
+                "basd_rank_certificate_scratch_bytes", "basd_sfadamw_launches"}
 
 _lock = threading.Lock()
 _lib = None

@@ -96,16 +96,22 @@ class FlatGradBucket:
         self._slot = (self._slot + 1) % len(self._slots)
         self.wait()
 
-    def wait(self, all_slots: bool = False) -> None:
+    def wait(self, all_slots: bool = False, *, divide: bool = True) -> bool:
         """Join the all-reduce queued on the current slot (every slot with ``all_slots``): the current stream waits
-        for the collective (RCCL: no host block) and the mean is completed where the backend only sums."""
+        for the collective (RCCL: no host block) and the mean is completed where the backend only sums.
+        ``divide=False`` leaves that division to the caller (an optimizer that folds ``1 / world`` into its own pass
+        over the gradients); returns whether a joined buffer still holds a SUM that was not divided."""
+        owed = False
         for i in (range(len(self._slots)) if all_slots else (self._slot,)):
             pending, self._pending[i] = self._pending[i], None
             if pending is not None:
-                work, divide = pending
+                work, needs_divide = pending
                 work.wait()
-                if divide:
+                if needs_divide and divide:
                     self._slots[i].div_(dist.get_world_size())
+                elif needs_divide:
+                    owed = True
+        return owed
 
     @property
     def student_view(self) -> torch.Tensor:

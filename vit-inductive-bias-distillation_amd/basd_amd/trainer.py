@@ -13,8 +13,10 @@ The models and the probing that produce ``teacher`` / ``student_info`` are the c
   in ONE flat RCCL all-reduce (``ddp.FlatGradBucket``): the reference leaves them out of ``accelerator.prepare``;
 * loaders are sharded with ``DistributedSampler`` (``shard_loader``).
 
-What is absent from the image and therefore replaced: ``schedulefree.AdamWScheduleFree`` (``torch.optim.AdamW``), ``accelerate`` (plain ``torch.distributed``),
-``torchvision.transforms.v2.MixUp / CutMix`` (``mixup_cutmix``).  No kernels here: torch module plumbing only.
+What is absent from the image and therefore replaced: ``accelerate`` (plain ``torch.distributed``),
+``torchvision.transforms.v2.MixUp / CutMix`` (``mixup_cutmix``).  The reference's optimizer, ``schedulefree.AdamWScheduleFree``,
+is provided by ``basd_amd.optim`` (one HIP launch per step) and selected with ``optimizer="schedulefree"``; the default stays
+``torch.optim.AdamW``.  No kernels here: torch module plumbing only.
 """
 from __future__ import annotations
 
@@ -76,10 +78,13 @@ class Trainer:
     ``.model.num_classes`` (the fields the reference constructor reads, trainer.py:52-93).  ``loss_cls`` defaults to
     the HIP-backed ``basd_amd.losses.BASDLoss``; tests on CPU hand in the oracle's class.
     ``autocast_dtype``: dtype of the model forward passes (``torch.bfloat16`` as ``Accelerator(mixed_precision="bf16")``,
-    or ``None``); the loss always sees fp32 logits and computes in fp32."""
+    or ``None``); the loss always sees fp32 logits and computes in fp32.
+    ``optimizer``: ``"adamw"`` (``torch.optim.AdamW``) or ``"schedulefree"`` (``basd_amd.optim.AdamWScheduleFree``, the
+    reference's choice, trainer.py:54-58; GPU only).  The schedule-free optimizer is kept in train mode except during
+    validation and while a checkpoint is taken, which see the averaged (eval-mode) weights."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
-                 autocast_dtype=None, mixup: bool = True) -> None:
+                 autocast_dtype=None, mixup: bool = True, optimizer: str = "adamw") -> None:
         self.config = config
         self.device = next(student_model.parameters()).device
         self.criterion = nn.CrossEntropyLoss(label_smoothing=config.training.label_smoothing)
@@ -94,9 +99,17 @@ class Trainer:
             student_depth=student_info["depth"], num_student_tokens=student_info["num_tokens"], config=config.basd,
             teacher_has_cls_token=teacher.has_cls_token,
         ).to(self.device)
-        self.optimizer = torch.optim.AdamW(student_model.parameters(), lr=config.training.learning_rate,
-                                           weight_decay=config.training.weight_decay)
+        if optimizer == "adamw":
+            self.optimizer = torch.optim.AdamW(student_model.parameters(), lr=config.training.learning_rate,
+                                               weight_decay=config.training.weight_decay)
+        elif optimizer == "schedulefree":
+            from .optim import AdamWScheduleFree
+            self.optimizer = AdamWScheduleFree(student_model.parameters(), lr=config.training.learning_rate,
+                                               weight_decay=config.training.weight_decay)
+        else:
+            raise ValueError(f"optimizer must be 'adamw' or 'schedulefree', not {optimizer!r}")
         self.optimizer.add_param_group({"params": list(self.basd_loss.parameters())})
+        self._optimizer_mode(True)
         self.autocast_dtype = autocast_dtype
         self.mixup = mixup
         self.best_val_acc = 0.0
@@ -116,6 +129,9 @@ class Trainer:
             self._bucket = FlatGradBucket(sum(p.numel() for p in self._params), list(self.basd_loss.parameters()),
                                           self.device)
             self._bucket.attach_grads(self._params)
+            if optimizer == "schedulefree":
+                # the gradients stay where they are: the update zeroes them in its own pass (no separate zero_grad)
+                self.optimizer.zero_grad_in_step = True
 
     # -- one batch: the body of the reference's _train_epoch loop (trainer.py:133-164)
     def train_step(self, batch: dict) -> dict:
@@ -135,21 +151,38 @@ class Trainer:
         # the loss is computed outside autocast: fp32 logits, tokens consumed in their own dtype (fp32 internal)
         loss = self.basd_loss(logits.float(), mixed_targets, s_tokens, teacher_tokens, teacher_attns)
         loss.backward()
-        self._all_reduce_gradients()
-        self.optimizer.step()
-        self.optimizer.zero_grad(set_to_none=False)
+        if getattr(self.optimizer, "zero_grad_in_step", False):
+            # schedule-free AdamW over the flat bucket: 1 / world (where the backend only sums) and the zeroing of the
+            # gradients are part of the one update launch
+            self.optimizer.step(grad_scale=self._all_reduce_gradients(divide=False))
+        else:
+            self._all_reduce_gradients()
+            self.optimizer.step()
+            self.optimizer.zero_grad(set_to_none=False)
         return {"loss": loss.detach(), "correct": logits.detach().argmax(1).eq(targets).sum(), "n": targets.size(0)}
 
-    def _all_reduce_gradients(self) -> None:
+    def _optimizer_mode(self, train: bool) -> bool:
+        """``optimizer.train()`` / ``optimizer.eval()`` where the optimizer has them (reference trainer.py:180,184);
+        returns whether it has."""
+        switch = getattr(self.optimizer, "train" if train else "eval", None)
+        if switch is None:
+            return False
+        switch()
+        return True
+
+    def _all_reduce_gradients(self, divide: bool = True) -> float:
         """The step's one exchange (reference trainer.py:157 leaves it to ``accelerator.backward``): mean over ranks of
         the flat gradient buffer, queued on the communicator's stream and joined by the current stream before the
-        optimizer reads the gradients -- which ARE the buffer (``attach_grads``), so nothing is packed or unpacked."""
+        optimizer reads the gradients -- which ARE the buffer (``attach_grads``), so nothing is packed or unpacked.
+        Returns the factor the caller still has to apply to the gradients: 1, or ``1 / world`` with ``divide=False``
+        on a backend that only sums."""
         if self._bucket is None:
-            return
+            return 1.0
         # a gradient autograd replaced (or never produced) goes back into the buffer; 0 in the steady state
         self.reattached += self._bucket.reattach_missing()
         self._bucket.all_reduce_mean(async_op=True)
-        self._bucket.wait()
+        owed = self._bucket.wait(divide=divide)
+        return 1.0 / dist.get_world_size() if owed else 1.0
 
     def _train_epoch(self, train_loader, epoch: int = 0) -> dict:
         # a sharded loader draws a different permutation every epoch only if it is told the epoch (every rank the same one)
@@ -160,6 +193,7 @@ class Trainer:
         correct = torch.zeros((), device=self.device, dtype=torch.long)
         total = 0
         self.model.train()
+        self._optimizer_mode(True)
         for batch in train_loader:
             out = self.train_step(batch)
             total_loss += out["loss"] * out["n"]
@@ -184,7 +218,10 @@ class Trainer:
             metrics = self._train_epoch(train_loader, epoch)
             if evaluate is not None and val_loader is not None:
                 self.model.eval()
+                switched = self._optimizer_mode(False)          # validation sees the averaged weights
                 metrics.update(evaluate(self.model, val_loader))
+                if switched:
+                    self._optimizer_mode(True)
             for key, value in metrics.items():
                 self.metrics_history[key].append(value)
             improved = metrics.get("val_acc", float("-inf")) > self.best_val_acc
@@ -197,9 +234,18 @@ class Trainer:
     # -- checkpoints: what accelerator.save_state + custom_state.pth hold in the reference (trainer.py:94-123)
     def state_dict(self, epoch: int) -> dict:
         self._finish_loss()
-        return {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(),
-                "basd_loss": self.basd_loss.state_dict(), "epoch": epoch, "best_val_acc": self.best_val_acc,
-                "metrics_history": dict(self.metrics_history)}
+        # a schedule-free optimizer is saved in eval mode (the reference saves after ``optimizer.eval()``): the weights
+        # are copied out, because they move back to the train-mode sequence before this returns
+        switched = self._optimizer_mode(False)
+        model, loss = self.model.state_dict(), self.basd_loss.state_dict()
+        if switched:
+            model = {k: v.clone() for k, v in model.items()}
+            loss = {k: v.clone() for k, v in loss.items()}
+        state = {"model": model, "optimizer": self.optimizer.state_dict(), "basd_loss": loss, "epoch": epoch,
+                 "best_val_acc": self.best_val_acc, "metrics_history": dict(self.metrics_history)}
+        if switched:
+            self._optimizer_mode(True)
+        return state
 
     def save_checkpoint(self, path: str, epoch: int) -> None:
         torch.save(self.state_dict(epoch), path)
@@ -209,6 +255,7 @@ class Trainer:
         self.model.load_state_dict(state["model"])
         self.optimizer.load_state_dict(state["optimizer"])
         self.basd_loss.load_state_dict(state["basd_loss"])
+        self._optimizer_mode(True)
         self.best_val_acc = state["best_val_acc"]
         self.metrics_history = defaultdict(list, state.get("metrics_history", {}))
         return state["epoch"] + 1
