@@ -664,6 +664,25 @@ int basd_sfadamw_swap(const BasdSfAdamwTensor* table, const int* chunks, int n_c
 /* diagnostics: kernel launches made by the two entry points above since the library was loaded (process-wide). */
 long basd_sfadamw_launches(void);
 
+/* ---- validation: loss, top-1 and top-k of one batch in one launch ------------------------------------ */
+
+/* replaces: the body of the batch loop of `evaluate_model`  src/evaluation/metrics.py:19-55 -- the column gather
+ * `outputs[:, valid_indices]`, `criterion(outputs, targets) * B`, and the two `MulticlassAccuracy.update` calls.
+ * logits: (B, C) fp32 / bf16 read in place with row stride ld (elements); class_index: K columns of it on the device
+ * (NULL with K == C: all classes in order); labels: B int64 positions in [0, K).  Per row b, with z_j the j-th selected
+ * logit and y = labels[b]:
+ *   loss_b = lse(z) - (1 - eps) z_y - eps / K sum_j z_j      (fp32, row maximum subtracted; not divided by a count;
+ *                                                              the last term is left out when eps == 0)
+ *   rank_b = #{j : z_j > z_y} + #{j < y : z_j == z_y}        (a tie goes to the lower class position)
+ * and, all by 64-bit integer atomic adds (agent scope), so that the result does not depend on the order of arrival:
+ *   state[0] += llrint(loss_b * 2^32);  state[1] += 1;  state[2] += rank_b == 0;  state[3] += rank_b < top_k.
+ * A row that cannot be represented -- y outside [0, K), a NaN among its K logits, loss_b not finite or >= 2^24, a
+ * class_index entry outside [0, C) (not read) -- is a miss at every k, adds 1 to state[4] and nothing to state[0].
+ * state: 5 words on the device, accumulated into (zero them to start).  ONE launch, no memset, no workspace; B == 0
+ * launches nothing.  1 <= top_k <= K. */
+int basd_eval_batch(const void* logits, int dtype, long ld, int B, int C, const int* class_index, int K,
+                    const long* labels, float label_smoothing, int top_k, long long* state, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ Sub-modules:
   ``ops``      torch.autograd Functions / host orchestration over the C-ABI
   ``losses``   ``BASDLoss`` / ``GrassmannianLayerSelector`` / free functions
   ``optim``    ``AdamWScheduleFree``: the reference trainer's optimizer, one launch per step
+  ``evaluation``  ``evaluate_model`` / ``EvalAccumulator``: top-1 / top-5 and loss, one launch per validation batch
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
 __version__ = "0.1.0"

@@ -16,7 +16,8 @@ The models and the probing that produce ``teacher`` / ``student_info`` are the c
 What is absent from the image and therefore replaced: ``accelerate`` (plain ``torch.distributed``),
 ``torchvision.transforms.v2.MixUp / CutMix`` (``mixup_cutmix``).  The reference's optimizer, ``schedulefree.AdamWScheduleFree``,
 is provided by ``basd_amd.optim`` (one HIP launch per step) and selected with ``optimizer="schedulefree"``; the default stays
-``torch.optim.AdamW``.  No kernels here: torch module plumbing only.
+``torch.optim.AdamW``.  Validation (``Trainer.evaluate``) is ``basd_amd.evaluation.evaluate_model``.  No kernels here: torch
+module plumbing only.
 """
 from __future__ import annotations
 
@@ -209,11 +210,21 @@ class Trainer:
         if sel is not None and hasattr(sel, "finish_pending"):
             sel.finish_pending()
 
+    def evaluate(self, model: nn.Module, val_loader) -> dict:
+        """The reference's validation call (trainer.py:185-189): ``evaluate_model`` with the trainer's smoothed
+        criterion -- one HIP launch per batch, one read-back per epoch; over the ranks' shards when a process group
+        with more than one rank exists.  Has the signature ``train(..., evaluate=)`` expects:
+        ``trainer.train(train_loader, val_loader, evaluate=trainer.evaluate)``."""
+        from .evaluation import evaluate_model
+        distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        return evaluate_model(model, val_loader, self.criterion, num_classes=self.config.model.num_classes,
+                              distributed=distributed)
+
     def train(self, train_loader, val_loader=None, start_epoch: int = 0, *, evaluate=None, on_epoch_end=None) -> dict:
         """The reference's epoch loop (trainer.py:171-216): ``_train_epoch``, validation, ``metrics_history``,
-        ``best_val_acc``.  Validation is the caller's (``evaluate(model, val_loader) -> {"val_acc": ...}``; the
-        reference's ``evaluate_model`` is outside this path); ``on_epoch_end(trainer, epoch, improved)`` is where a
-        caller saves checkpoints."""
+        ``best_val_acc``.  Validation is the caller's (``evaluate(model, val_loader) -> {"val_acc": ...}``): pass
+        ``evaluate=trainer.evaluate`` for the reference's ``evaluate_model``; ``on_epoch_end(trainer, epoch, improved)``
+        is where a caller saves checkpoints."""
         for epoch in range(start_epoch, self.config.training.num_epochs):
             metrics = self._train_epoch(train_loader, epoch)
             if evaluate is not None and val_loader is not None:
