@@ -10,7 +10,8 @@
  *   - no entry point allocates, frees or synchronises; all work is queued on `stream`
  *     (pass torch.cuda.current_stream().cuda_stream); scratch buffers are caller-provided;
  *   - return value: 0 = ok, <0 = invalid argument / unsupported shape (BASD_E*), >0 = hipError_t;
- *   - dtype codes: 0 = fp32, 1 = bf16 (inputs only; all arithmetic and outputs are fp32/fp64);
+ *   - dtype codes: 0 = fp32, 1 = bf16 (inputs only; all arithmetic and outputs are fp32/fp64), 2 = uint8 (image
+ *     batches of basd_mix_batch only, which is also the one entry point that may write bf16);
  *   - entry points are re-entrant and keep no global mutable state, with a few process-wide test / tuning hooks as the
  *     only exceptions: basd_tridiag_tuning, basd_jacobi_tuning, basd_jacobi_ordering, basd_gemm_tuning, basd_procrustes_tuning (none is called by the
  *     loss), and the launch counter behind basd_sfadamw_launches (diagnostics).
@@ -33,6 +34,7 @@ typedef struct ihipStream_t* hipStream_t;
 #define BASD_EUNSUPPORTED (-2)
 #define BASD_DTYPE_F32 0
 #define BASD_DTYPE_BF16 1
+#define BASD_DTYPE_U8 2    /* basd_mix_batch sources only */
 
 /* ---- dense contractions (fp32 MFMA, v_mfma_f32_32x32x2_f32) ------------------------------- */
 
@@ -682,6 +684,32 @@ long basd_sfadamw_launches(void);
  * launches nothing.  1 <= top_k <= K. */
 int basd_eval_batch(const void* logits, int dtype, long ld, int B, int C, const int* class_index, int K,
                     const long* labels, float label_smoothing, int top_k, long long* state, hipStream_t stream);
+
+/* ---- batch preparation: MixUp / CutMix, soft targets and the uint8 conversion in one launch ------------ */
+
+/* Channels that may carry their own mean / std (they travel in the kernel arguments). */
+#define BASD_MIX_MAX_STAT_CHANNELS 4
+
+/* replaces: `self.mixup_cutmix(images, targets)`  src/training/trainer.py:89-92, :141 (RandomChoice([MixUp, CutMix]) of
+ * torchvision.transforms.v2 incl. the one-hot soft targets), and for uint8 sources the loader's
+ * `ToDtype(float32, scale=True)` + `Normalize(mean, std)`.
+ * src: dense NCHW (B, C, H, W), fp32 / bf16 / uint8 (BASD_DTYPE_U8); dst: dense NCHW of the same shape, fp32 / bf16,
+ * not overlapping src (checked).  The partner of row i is row (i - 1) mod B (`roll(1, 0)`).  Every step below is ONE
+ * fp32 operation rounded to nearest, nothing is contracted; a bf16 dst is rounded once, to nearest even, at the end.
+ *   v(x) = float(x)  (fp32, bf16);   v(u) = ((float(u) / 255) - mean_c) / std_c  (uint8, two true divisions;
+ *                                     mean = std = NULL: mean 0, std 1 for any C; otherwise C <= 4 floats each, HOST)
+ *   kind 0 (none):    out = v(x_i)
+ *   kind 1 (MixUp):   out = v(x_{i-1}) * fp32(1.0 - lam) + v(x_i) * fp32(lam)                (1.0 - lam in double)
+ *   kind 2 (CutMix):  out = v(x_{i-1}) for y1 <= y < y2 and x1 <= x < x2, v(x_i) elsewhere   (an empty box: a copy)
+ * labels (nullable; B int64 on the device) given: targets, dense (B, K) fp32, is written whole in the same launch,
+ *   T[i][k] = [y_{i-1} == k] * fp32(1.0 - lam_targets) + [y_i == k] * fp32(lam_targets);
+ * a label outside [0, K) in row i or in its partner makes row i of T NaN (nothing is read or written out of bounds).
+ * ONE launch, no memset, no workspace, no host-to-device copy; B == 0 launches nothing.  16-byte accesses where the
+ * rows' addresses allow, narrower ones for rows at other offsets and for the last C*H*W % width elements. */
+int basd_mix_batch(const void* src, int src_dtype, void* dst, int dst_dtype, int B, int C, int H, int W, int kind,
+                   double lam, int y1, int y2, int x1, int x2, const float* mean /* host */,
+                   const float* std /* host */, const long* labels, int K, double lam_targets, float* targets,
+                   hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,8 @@ Sub-modules:
   ``losses``   ``BASDLoss`` / ``GrassmannianLayerSelector`` / free functions
   ``optim``    ``AdamWScheduleFree``: the reference trainer's optimizer, one launch per step
   ``evaluation``  ``evaluate_model`` / ``EvalAccumulator``: top-1 / top-5 and loss, one launch per validation batch
+  ``augment``  ``BatchMixer`` / ``draw_mix_params``: MixUp / CutMix, soft targets and the uint8 conversion, one launch
+               per batch
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
 __version__ = "0.1.0"

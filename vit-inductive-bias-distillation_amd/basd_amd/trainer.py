@@ -14,7 +14,8 @@ The models and the probing that produce ``teacher`` / ``student_info`` are the c
 * loaders are sharded with ``DistributedSampler`` (``shard_loader``).
 
 What is absent from the image and therefore replaced: ``accelerate`` (plain ``torch.distributed``),
-``torchvision.transforms.v2.MixUp / CutMix`` (``mixup_cutmix``).  The reference's optimizer, ``schedulefree.AdamWScheduleFree``,
+``torchvision.transforms.v2.MixUp / CutMix`` (``mixup_cutmix`` with torch ops, or ``mixup="fused"``: ``basd_amd.augment``, one
+HIP launch per batch that also converts and normalises uint8 batches).  The reference's optimizer, ``schedulefree.AdamWScheduleFree``,
 is provided by ``basd_amd.optim`` (one HIP launch per step) and selected with ``optimizer="schedulefree"``; the default stays
 ``torch.optim.AdamW``.  Validation (``Trainer.evaluate``) is ``basd_amd.evaluation.evaluate_model``.  No kernels here: torch
 module plumbing only.
@@ -82,10 +83,16 @@ class Trainer:
     or ``None``); the loss always sees fp32 logits and computes in fp32.
     ``optimizer``: ``"adamw"`` (``torch.optim.AdamW``) or ``"schedulefree"`` (``basd_amd.optim.AdamWScheduleFree``, the
     reference's choice, trainer.py:54-58; GPU only).  The schedule-free optimizer is kept in train mode except during
-    validation and while a checkpoint is taken, which see the averaged (eval-mode) weights."""
+    validation and while a checkpoint is taken, which see the averaged (eval-mode) weights.
+    ``mixup``: ``True`` (``mixup_cutmix``, torch ops), ``False``, or ``"fused"`` (``basd_amd.augment.BatchMixer``: mixing, soft
+    targets and the uint8 conversion in one HIP launch; GPU only).  ``image_stats``: ``{"clean": (mean, std), "augmented":
+    (mean, std)}`` per channel; with it (and ``mixup="fused"``) the loader may hand over uint8 batches: ``augmented`` is
+    normalised inside the mixing launch, ``clean`` by a convert-only launch with the teacher's statistics.  A uint8 batch
+    without it, or with another ``mixup``, raises ``TypeError``.  ``mix_dtype``: dtype the fused launches write
+    (``torch.bfloat16``: what autocast would cast the images to anyway; default: fp32 for uint8, else the batch's own)."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
-                 autocast_dtype=None, mixup: bool = True, optimizer: str = "adamw") -> None:
+                 autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None) -> None:
         self.config = config
         self.device = next(student_model.parameters()).device
         self.criterion = nn.CrossEntropyLoss(label_smoothing=config.training.label_smoothing)
@@ -112,7 +119,23 @@ class Trainer:
         self.optimizer.add_param_group({"params": list(self.basd_loss.parameters())})
         self._optimizer_mode(True)
         self.autocast_dtype = autocast_dtype
+        if mixup not in (True, False, "fused"):
+            raise ValueError(f"mixup must be True, False or 'fused', not {mixup!r}")
         self.mixup = mixup
+        self.image_stats = image_stats
+        self._mixer = self._clean_mixer = None
+        if image_stats is not None and set(image_stats) != {"clean", "augmented"}:
+            raise ValueError(f"image_stats needs the keys 'clean' and 'augmented' (got {sorted(image_stats)})")
+        if mixup == "fused":
+            from .augment import BatchMixer
+            stats = image_stats or {"clean": (None, None), "augmented": (None, None)}
+            classes = config.model.num_classes
+            self._mixer = BatchMixer(classes, mean=stats["augmented"][0], std=stats["augmented"][1],
+                                     out_dtype=mix_dtype, device=self.device)
+            self._clean_mixer = BatchMixer(classes, mean=stats["clean"][0], std=stats["clean"][1],
+                                           out_dtype=mix_dtype, device=self.device)
+        elif mix_dtype is not None:
+            raise ValueError("mix_dtype needs mixup='fused'")
         self.best_val_acc = 0.0
         self.metrics_history = defaultdict(list)
         self._params = [p for p in student_model.parameters() if p.requires_grad]
@@ -141,7 +164,18 @@ class Trainer:
         student_imgs = batch["augmented"].to(dev, non_blocking=True)
         targets = batch["label"].to(dev, non_blocking=True)
         mixed_targets = targets
-        if self.mixup:
+        if clean.dtype == torch.uint8 or student_imgs.dtype == torch.uint8:
+            if self.mixup != "fused" or self.image_stats is None:
+                raise TypeError("uint8 batches need mixup='fused' and image_stats (the conversion and the normalisation "
+                                f"are part of the fused launch); got mixup={self.mixup!r}, image_stats="
+                                f"{'given' if self.image_stats is not None else None}, clean {clean.dtype} "
+                                f"{tuple(clean.shape)}, augmented {student_imgs.dtype} {tuple(student_imgs.shape)}")
+        if self.mixup == "fused":
+            from .augment import MixParams
+            if clean.dtype == torch.uint8:
+                clean, _ = self._clean_mixer(clean, None, MixParams("none"))
+            student_imgs, mixed_targets = self._mixer(student_imgs, targets)
+        elif self.mixup:
             student_imgs, mixed_targets = mixup_cutmix(student_imgs, targets, self.config.model.num_classes)
         ac = torch.autocast(dev.type, dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None)
         with ac:

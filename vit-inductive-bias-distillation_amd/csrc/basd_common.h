@@ -10,6 +10,7 @@
 
 #define BASD_DTYPE_F32 0
 #define BASD_DTYPE_BF16 1
+#define BASD_DTYPE_U8 2
 
 #define BASD_CHECK_ARG(cond) \
     do {                     \
