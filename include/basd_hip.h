@@ -287,10 +287,9 @@ int basd_flag_set(unsigned* flag, unsigned value, hipStream_t stream);
  *             teacher's projections);
  *         1 = teacher matrices first; the student side (Grams + factorisation, student_stream != chain_stream) is
  *             held back until the ranks are out;   2 = the same, not held back;
- *         3 = the same, held back until the teacher's Grams are done (ev_tg0) plus `release_delay` rounds of ~3.4 us:
+ *         3 = the same, held back until the teacher's Grams are done (ev_tg0):
  *             the student Grams -- the largest MFMA launch of the step -- then run beside the teacher's
- *             factorisation (two CUs) instead of beside its projection and Grams, and that factorisation's whole-CU
- *             workgroups have been placed before the student side's launches refill every free slot.
+ *             factorisation (two CUs) instead of beside its projection and Grams.
  *   streams: main_stream = the caller's (inputs are ready there; NULL: the caller has recorded ev_fork on it already,
  *         e.g. before it queued other work the chain need not wait for); events are opaque handles of basd_event_create:
  *         ev_fork / ev_student / ev_ranks / ev_tail / ev_tgram / ev_tg0 are recorded by the call; ev_slot_free (nullable) is waited for
@@ -326,7 +325,6 @@ typedef struct BasdSelectorChain {
     int* k_arr; const int* sw_index; int* jflags;
     hipStream_t main_stream, chain_stream, student_stream, tail_stream;
     void* ev_fork; void* ev_student; void* ev_ranks; void* ev_tail; void* ev_slot_free; void* ev_tgram; void* ev_tg0;
-    long release_delay;                    /* mode 3: rounds of ~3.4 us between the teacher's factorisation launch and the student side's release */
     /* mode 3, nullable: the teacher's factorisation is queued FIRST, on fact_stream, and waits for go_flag (one device
      * word of the slot, set behind the teacher Grams to go_value != 0): see basd_tridiag_ranked_gated.  ev_ranks is then
      * recorded on fact_stream. */
@@ -432,16 +430,10 @@ int basd_procrustes_finalize(const float* w, long w_batch_stride, const float* s
                              const int* tap1, const float* lam, const float* tr_s_part, int tr_slabs, float* tr_s,
                              float* tr_t, float* nuc, float* loss, float* k_prime, hipStream_t stream);
 
-/* dX = (*scale_ptr * scale_const) * w_s * ((x_s - mu) - interp(K' A')[s]): autograd of relational.py:36-50
- * with respect to the student tokens. */
-int basd_student_grad(const void* x, int dtype, long sb, long sn, int B, int n_s, int n_t, int D, const float* omega,
-                      const float* mu, const float* h, const int* tap0, const int* tap1, const float* lam,
-                      const float* scale_ptr, float scale_const, float* dx, const float* tnorm2, float* gomega,
-                      hipStream_t stream);
-
-/* basd_student_project / basd_student_grad for all E extraction layers in ONE launch each.  x_ptrs: device table of
- * E base pointers (common strides); omega + e * omega_e_stride (0 = one weight vector for all layers); the other
- * operands are laid out (E, B, ...); scale_ptr[e] = upstream gradient of layer e.
+/* basd_student_project, and the student gradient dX = (*scale_ptr * scale_const) * w_s * ((x_s - mu) - interp(K' A')[s])
+ * (autograd of relational.py:36-50 with respect to the student tokens), for all E extraction layers in ONE launch each.
+ * x_ptrs: device table of E base pointers (common strides); omega + e * omega_e_stride (0 = one weight vector for all
+ * layers); the other operands are laid out (E, B, ...); scale_ptr[e] = upstream gradient of layer e.
  * basd_student_project_multi returns BASD_EUNSUPPORTED where its vectorised LDS-staged kernel does not apply (rows not
  * 16-byte aligned, slab over 64 KB): fall back to basd_student_project per layer. */
 int basd_student_project_multi(const void* const* x_ptrs, int dtype, long sb, long sn, int E, int B, int n_s, int n_t,
@@ -556,7 +548,6 @@ int basd_event_destroy(void* event);
 int basd_stream_wait_event(hipStream_t stream, void* event);
 int basd_event_record(void* event, hipStream_t stream);
 int basd_event_synchronize(void* event);      /* blocks the calling host thread */
-int basd_event_query(void* event);            /* 1 = reached, 0 = not yet, < 0 = invalid */
 /* A stream of priority level -1 (highest of the device's range), 0 (default) or +1 (lowest). */
 int basd_stream_create_priority(void** out, int level);
 /* diagnostics: events that carry a time stamp (basd_event_create makes them without), and the time between two */

@@ -86,7 +86,6 @@ SIGNATURES = {
     "basd_ustack_from_transposed": [vp, i64, vp, i32, i32, vp, i64, vp, i64, vp, i32, vp, vp],
     "basd_resample_tokens": [vp, i32, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "basd_resample_tokens_adjoint": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
-    "basd_student_grad": [vp, i32, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp],
     "basd_teacher_factor": [vp, i64, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "basd_teacher_factor_tiled": [vp, i64, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "basd_mix_grad_tokens": [vp, vp, i32, i32, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp],
@@ -105,7 +104,6 @@ SIGNATURES = {
     "basd_jacobi_lds_square_fits": [i32],
     "basd_event_record": [vp, vp],
     "basd_event_synchronize": [vp],
-    "basd_event_query": [vp],
     "basd_stream_create_priority": [vp, i32],
     "basd_event_create_timed": [vp],
     "basd_event_elapsed_ms": [vp, vp, vp],
@@ -153,7 +151,7 @@ class SelectorChainArgs(C.Structure):
                              "student_status_mirror", "zv", "vecs", "u_rot", "sw", "cos", "sigma", "d_out", "k_arr",
                              "sw_index", "jflags", "main_stream", "chain_stream", "student_stream", "tail_stream",
                              "ev_fork", "ev_student", "ev_ranks", "ev_tail", "ev_slot_free", "ev_tgram", "ev_tg0",
-                             "release_delay", "fact_stream", "go_flag", "go_value", "go_budget",
+                             "fact_stream", "go_flag", "go_value", "go_budget",
                              "tm_proj", "tm_tgram", "tm_scol0", "tm_scol1", "tm_sgram", "tm_tri0", "tm_mid", "tm_spec",
                              "cert_stream", "cert_mirror", "ev_cert", "cert_scratch")]
     )

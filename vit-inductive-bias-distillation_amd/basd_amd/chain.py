@@ -17,7 +17,6 @@ from . import _lib, ops
 
 import os
 
-RELEASE_DELAY = int(os.environ.get("BASD_CHAIN_RELEASE_DELAY", "0"))      # mode 3, rounds of ~3.4 us (BasdSelectorChain.release_delay)
 # mode 3: queue the teacher's factorisation FIRST, on a stream of its own, gated by a device word behind the Grams
 # (basd_tridiag_ranked_gated): its whole-CU workgroups hold their CUs before the step's throughput launches fill the chip
 EARLY_LAUNCH = os.environ.get("BASD_CHAIN_EARLY", "0") == "1"      # measured: ranks 0.3 ms earlier, step 0.1 ms LONGER
@@ -115,7 +114,6 @@ class _Slot:
         a.ev_fork, a.ev_student, a.ev_ranks, a.ev_tail = self.ev_fork, self.ev_student, self.ev_ranks, self.ev_tail
         a.ev_tgram = self.ev_tgram
         a.ev_tg0 = self.ev_tg0
-        a.release_delay = RELEASE_DELAY
         if p.cert_stream is not None:
             b["cert_scratch"] = torch.zeros((_lib.query("basd_rank_certificate_scratch_bytes", L),), device=dev,
                                             dtype=torch.uint8)
@@ -177,19 +175,11 @@ class SelectorChainPlan:
             return k
         return 0
 
-    def fork(self, main_stream: int) -> None:
-        """Mark the point of the caller's stream the NEXT ``queue`` may start behind (its inputs are ready there); work the
-        caller queues after this call is not waited for by the chain."""
-        _lib.call("basd_event_record", self.slots[self.turn].ev_fork, main_stream)
-        self._forked = True
-
     def queue(self, students, teachers, proj_t: torch.Tensor, proj_s_t: torch.Tensor, main_stream: int) -> _Slot:
         """Queue the whole selector of this step; returns the slot whose ``ev_ranks`` / ``mirror`` the host reads."""
         slot = self.slots[self.turn]
         self.turn = (self.turn + 1) % len(self.slots)
         a = slot.args
-        if getattr(self, "_forked", False):
-            main_stream, self._forked = None, False
         for l, t in enumerate(teachers):
             slot.teacher_ptrs[l] = t.data_ptr()
         a.student_ptrs = ops._ptr_table(students).data_ptr()

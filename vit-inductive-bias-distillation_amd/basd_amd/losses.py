@@ -9,6 +9,7 @@ raises ``RuntimeError`` (no fallback path exists).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 
@@ -119,6 +120,24 @@ def _single_member_mode(why: str) -> None:
     warnings.warn("basd_tridiag: " + why + "; switching the tridiagonalisation to one workgroup per matrix "
                   "(no inter-workgroup hand-off; slower first stage) for the rest of this process", RuntimeWarning)
     ops._lib.call("basd_tridiag_tuning", 1, -1, -1, -1, -1, 0)
+
+
+def _rank_zero_error() -> torch.linalg.LinAlgError:
+    """What the reference's forward raises for a teacher layer of Marchenko-Pastur rank 0: 0/0 distance -> NaN weights ->
+    NaN tokens -> torch.linalg.svd raises."""
+    return torch.linalg.LinAlgError(
+        "linalg.svd: The algorithm failed to converge because the input matrix contained "
+        "non-finite values (a teacher layer has Marchenko-Pastur rank 0).")
+
+
+def _record_events(streams) -> list:
+    """One fresh event recorded on each of ``streams``."""
+    events = []
+    for stream in streams:
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        events.append(ev)
+    return events
 
 
 def _record_stream(obj, stream) -> None:
@@ -338,24 +357,10 @@ class _GrassmannDistance(torch.autograd.Function):
     @staticmethod
     def forward(ctx, selector, keys, teachers, *students):
         want_grad = any(s.requires_grad for s in students)
-        # the student side (E Grams + eigen-solves) is independent of the teacher side (2L) and may take its own stream,
-        # joined where the cosine matrices need both.  OFF by default: at cfg-4 the two shared tridiagonalisation stages
-        # side by side cost more than queueing them behind each other (63.7 vs 58.3 ms per step)
-        ss = selector._student_side_stream(students[0].device) if selector.overlap_student_side else None
 
         def run():
-            if ss is not None:
-                ss.wait_stream(torch.cuda.current_stream())
-                for s in students:
-                    s.record_stream(ss)
-            spectra = selector._spectra_async(list(students), teachers, all_student_vectors=want_grad, student_stream=ss,
-                                              gate_student=False)
-            out = selector._angles_from_spectra(spectra, keys, want_grad=want_grad)
-            if ss is not None:
-                # allocated on the student stream, kept for the backward on this one
-                _record_stream([spectra.get("s_ts"), spectra.get("means"), spectra.get("s_stack"),
-                                spectra.get("s_colnorm"), out[1]], torch.cuda.current_stream())
-            return out
+            spectra = selector._spectra_async(list(students), teachers, all_student_vectors=want_grad)
+            return selector._angles_from_spectra(spectra, keys, want_grad=want_grad)
         try:
             d, saved = run()
         except TridiagGiveUp as exc:       # degrade, do not die: once more with one workgroup per matrix
@@ -455,11 +460,9 @@ class GrassmannianLayerSelector(nn.Module):
         self.teacher_space_gram = os.environ.get("BASD_TEACHER_SPACE_GRAM", "1") != "0"
         self.rank1_mp = os.environ.get("BASD_RANK1_MP", "1") != "0"
         self.merge_factorisations = os.environ.get("BASD_MERGE_FACTORISATIONS", "1") != "0"   # cfg-4: 46.4 -> ? ms
-        self.overlap_student_side = os.environ.get("BASD_OVERLAP_STUDENT_SIDE", "0") != "0"    # measured: 63.7 vs 58.3 ms at cfg-4
         # backward of multi-layer teachers at student orders the LDS-resident Jacobi solver takes: full Jacobi eigenvectors
         # (see ``_spectra_async``); False keeps the tridiagonal route of larger students (tests cover it at small shapes)
         self.small_student_jacobi = True
-        self._student_streams: dict = {}
 
         # Same global-RNG consumption order as the reference (proj_s, then proj_t), on CPU.
         proj_s = torch.empty(student_dim, student_dim)
@@ -577,12 +580,6 @@ class GrassmannianLayerSelector(nn.Module):
         for k, r in zip(keys, ranks_dev.tolist()):
             self._subspace_ranks[k] = int(r)
 
-    def _student_side_stream(self, device) -> "torch.cuda.Stream":
-        key = str(device)
-        if key not in self._student_streams:
-            self._student_streams[key] = torch.cuda.Stream(device=device)
-        return self._student_streams[key]
-
     def _proj_s_transposed(self) -> torch.Tensor:
         """proj_s^T, fp32 contiguous; cached (the buffer only changes on load_state_dict / .to())."""
         key = (self.proj_s.data_ptr(), self.proj_s._version, self.proj_s.dtype)
@@ -594,8 +591,7 @@ class GrassmannianLayerSelector(nn.Module):
     # ---- distances + mixing weights ------------------------------------------------------
     @torch.no_grad()
     def _spectra_async(self, students: list[torch.Tensor], teachers: list[torch.Tensor],
-                       all_student_vectors: bool = False, student_stream=None, defer_student: bool = False,
-                       gate_student: bool = True) -> dict:
+                       all_student_vectors: bool = False, student_stream=None, defer_student: bool = False) -> dict:
         """Queue every Gram matrix and eigen-solve of the step; no host sync.
         (layer_selector.py:69-74, :131-138, :86-92)
 
@@ -654,7 +650,7 @@ class GrassmannianLayerSelector(nn.Module):
                     st["s_stack"], st["s_colnorm"] = s_stack, ops.jacobi_onesided(s_stack, d_s)
                 else:
                     s_ts = ops.tridiagonalise(s_stack)
-                    if student_stream is not None and gate_student:
+                    if student_stream is not None:
                         # status word of this factorisation: read by the host one step later (it never waits
                         # for the student chain)
                         st["student_status"] = self._queue_readback([s_ts.err], "student")
@@ -669,7 +665,7 @@ class GrassmannianLayerSelector(nn.Module):
         # chain ~1 ms (rocprofv3: teacher Grams 0.46 ms instead of 0.06, shared stage 0.72 instead of 0.48).  So it is
         # queued BEHIND the teacher chain and gated on an event recorded after that stage -- from there on the teacher
         # factorisation sits in one CU per matrix and no longer cares.
-        gated = student_stream is not None and tri and self.gate_student_chain and gate_student
+        gated = student_stream is not None and tri and self.gate_student_chain
         if (tri and not stud_jacobi and self.rank1_mp and self.merge_factorisations and student_stream is None
                 and self._teacher_space_route(teachers)):
             # ONE factorisation launch over the L centred teacher Grams and the E student Grams (multi-layer ViT teachers:
@@ -828,10 +824,7 @@ class GrassmannianLayerSelector(nn.Module):
         for k, r in zip(keys, ranks):
             self._subspace_ranks[k] = r
         if min(ranks) == 0:
-            # reference: 0/0 distance -> NaN weights -> NaN tokens -> torch.linalg.svd raises
-            raise torch.linalg.LinAlgError(
-                "linalg.svd: The algorithm failed to converge because the input matrix contained "
-                "non-finite values (a teacher layer has Marchenko-Pastur rank 0).")
+            raise _rank_zero_error()
         return ranks
 
     @torch.no_grad()
@@ -987,9 +980,7 @@ class GrassmannianLayerSelector(nn.Module):
         x = ops.as_supported(s_tokens)
         kmax = max(int(self.subspace_ranks[t]) for t in teacher_indices)
         if kmax < 1:
-            raise torch.linalg.LinAlgError(
-                "linalg.svd: The algorithm failed to converge because the input matrix contained "
-                "non-finite values (a teacher layer has Marchenko-Pastur rank 0).")
+            raise _rank_zero_error()
         gram, _ = ops.centered_grams([x])                                     # :88-91 (proj_s folded below)
         ts = ops.tridiag_eigenvalues(gram)
         v_s = ops.tridiag_eigenvectors(ts, kmax)[0]                           # (kmax, d_s): Vt of the raw tokens
@@ -1093,10 +1084,7 @@ class BASDLoss(nn.Module):
         # that follow one whose ranks had to be waited for (2.38 against 2.46))
         self._chain_mode_forced = int(os.environ["BASD_CHAIN_MODE"]) if "BASD_CHAIN_MODE" in os.environ else None
         self._last_step_waited = False
-        # which of the step's two chains the host queues first: the Procrustes kernels of the caller's stream or the selector
-        self.procrustes_first = os.environ.get("BASD_PROCRUSTES_FIRST", "0") == "1"
         self.student_low_priority = os.environ.get("BASD_STUDENT_LOW_PRIORITY", "1") == "1"
-        self.tail_low_priority = os.environ.get("BASD_TAIL_LOW_PRIORITY", "0") != "0"
         self._chain_plans: dict = {}
 
     def _selector_stream(self, device, index: int = 0) -> "torch.cuda.Stream":
@@ -1166,11 +1154,7 @@ class BASDLoss(nn.Module):
             with torch.cuda.stream(side):
                 queue_student()
         # what the selector tail of THIS step has to wait for (it may be queued after later steps' chains)
-        chain_done = []
-        for st_ in (side, side2):
-            ev = torch.cuda.Event()
-            ev.record(st_)
-            chain_done.append(ev)
+        chain_done = _record_events((side, side2))
         tail = self._selector_stream(main.device, 3 * lane + 2)
 
         def read_ranks_once():
@@ -1191,11 +1175,7 @@ class BASDLoss(nn.Module):
                 torch.cuda.synchronize(main.device)
                 with torch.cuda.stream(side):
                     spectra = sel._spectra_async(students, teachers, student_stream=side2)
-                chain_done = []
-                for st_ in (side, side2):
-                    ev = torch.cuda.Event()
-                    ev.record(st_)
-                    chain_done.append(ev)
+                chain_done = _record_events((side, side2))
                 return read_ranks_once()
 
         def queue_tail(ranks, gate_tail=False):
@@ -1241,23 +1221,11 @@ class BASDLoss(nn.Module):
                 # offers high / default), so that the dispatcher serves the two chains the step waits for first
                 key_s = (str(main.device), "student-low")
                 if key_s not in self._side_streams:
-                    import ctypes
                     h = ctypes.c_void_p()
                     with torch.cuda.device(main.device):
                         ops._lib.call("basd_stream_create_priority", ctypes.byref(h), 1)
                     self._side_streams[key_s] = torch.cuda.ExternalStream(h.value, device=main.device)
                 streams[1] = self._side_streams[key_s]
-            if self.tail_low_priority:
-                # ... and so is the selector's tail (its d_grass_sq is only published)
-                key_t = (str(main.device), "tail-low")
-                if key_t not in self._side_streams:
-                    import ctypes
-                    h = ctypes.c_void_p()
-                    with torch.cuda.device(main.device):
-                        ops._lib.call("basd_stream_create_priority", ctypes.byref(h), 1)
-                    self._side_streams[key_t] = torch.cuda.ExternalStream(h.value, device=main.device)
-                streams[2] = self._side_streams[key_t]
-            streams = tuple(streams)
             plan = self._chain_plans[key] = SelectorChainPlan(students, teachers, self.chain_mode, streams,
                                                               fact_stream=self._selector_stream(main.device, 3))
         return plan
@@ -1279,21 +1247,14 @@ class BASDLoss(nn.Module):
         proj_t = sel.proj_t if sel.proj_t.dtype == torch.float32 and sel.proj_t.is_contiguous() \
             else sel.proj_t.float().contiguous()
         ops.gpu_mark("chain_begin")
-        slot = None
-        if self.procrustes_first:
-            plan.fork(main.cuda_stream)        # the chain starts behind THIS point, not behind the kernels queued next
-        else:
-            slot = plan.queue(xs, teachers, proj_t, sel._proj_s_transposed(), main.cuda_stream)
-            ops.trace("chains_queued")
+        slot = plan.queue(xs, teachers, proj_t, sel._proj_s_transposed(), main.cuda_stream)
+        ops.trace("chains_queued")
         ce_loss = _base_loss(self.base_criterion, student_output, targets)
         # softmax over ONE logit: the mixing weights are exactly 1 and d loss / d temperature exactly 0
         mix = ops._device_consts((1.0,) * len(students), torch.float32, main.device).view(-1, 1)
         total, geo_layers = _SingleTeacherTotal.apply(ce_loss, bool(self.teacher_has_cls_token),
                                                       sel.log_temperatures, teachers, attns, *students)
         ops.trace("procrustes_queued")
-        if slot is None:
-            slot = plan.queue(xs, teachers, proj_t, sel._proj_s_transposed(), main.cuda_stream)
-            ops.trace("chains_queued")
 
         # the step's inputs, for the two redo paths below; dropped when the read-back is left to the next call, so that a
         # pending read-back does not keep a whole step's token tensors alive (a failed factorisation is then not redone:
@@ -1337,10 +1298,7 @@ class BASDLoss(nn.Module):
                     raise TridiagGiveUp(f"basd_tridiag: the factorisation failed with one workgroup per matrix [{status}]")
             sel._subspace_ranks[keys[0]] = int(ranks[0])
             if min(ranks) == 0:
-                # reference: 0/0 distance -> NaN weights -> NaN tokens -> torch.linalg.svd raises
-                raise torch.linalg.LinAlgError(
-                    "linalg.svd: The algorithm failed to converge because the input matrix contained "
-                    "non-finite values (a teacher layer has Marchenko-Pastur rank 0).")
+                raise _rank_zero_error()
             # layer_selector.py:99-105: nothing of THIS loss reads it; published as ``last_components["d_grass_sq"]``
             # (written on the selector's tail stream: synchronise the device before reading it)
             comp["d_grass_sq"] = plan.finish_tail(slot, ranks)

@@ -133,13 +133,6 @@ __global__ void __launch_bounds__(256) debug_fill_lds_kernel(unsigned pattern, i
     if (fill_words[(threadIdx.x * 97) % words] != pattern) __builtin_trap();      // keeps the stores
 }
 
-// A fixed delay (no memory polling: it cannot deadlock, whatever runs or does not run beside it): one wave asleep for
-// ~3.4 us x `rounds` at 2.4 GHz.  Queued at the head of the student side (mode 3), which the teacher's Grams release: the whole-CU factorisation workgroups of the teacher side, released by the same Grams on
-// another stream, get their CUs BEFORE the student side's throughput launches refill every free slot.
-__global__ void chain_delay_kernel(int rounds) {
-    for (int i = 0; i < rounds; ++i) __builtin_amdgcn_s_sleep(127);
-}
-
 }  // namespace basd
 
 #define BASD_TRY(call)                \
@@ -192,14 +185,6 @@ int basd_event_elapsed_ms(void* from, void* to, float* ms_out) {
     BASD_CHECK_ARG(from && to && ms_out);
     BASD_HIP(hipEventElapsedTime(ms_out, (hipEvent_t)from, (hipEvent_t)to));
     return BASD_OK;
-}
-// 1 when everything recorded before the event has completed, 0 when not yet
-int basd_event_query(void* ev) {
-    if (!ev) return BASD_EINVAL;
-    const hipError_t e = hipEventQuery((hipEvent_t)ev);
-    if (e == hipSuccess) return 1;
-    if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-    return BASD_EINVAL;
 }
 
 // layer_selector.py:36-37, :92, :95-105 for the matrices of one chain: spectra of the L centred teacher and E student
@@ -380,12 +365,8 @@ int basd_selector_chain(const BasdSelectorChain* a) {
         }
         BASD_CHECK_ARG(a->tri_work_s != nullptr && ss != cs);
         if (mode == 1) BASD_HIP(hipStreamWaitEvent(ss, (hipEvent_t)a->ev_ranks, 0));
-        if (mode == 3) {
-            // released by the teacher's Grams like the teacher's factorisation (queued above on `cs`), but a short fixed
-            // delay later: that factorisation's whole-CU workgroups are placed first
-            BASD_HIP(hipStreamWaitEvent(ss, (hipEvent_t)a->ev_tg0, 0));
-            if (a->release_delay > 0) basd::chain_delay_kernel<<<1, 64, 0, ss>>>((int)a->release_delay);
-        }
+        // mode 3: released by the teacher's Grams, like the teacher's factorisation (queued above on `cs`)
+        if (mode == 3) BASD_HIP(hipStreamWaitEvent(ss, (hipEvent_t)a->ev_tg0, 0));
         BASD_TRY(student_grams(ss));
         BASD_TRY(basd_tridiag(a->grams + 2L * L * nn, nn, n, E, a->d + 2L * L * n, a->e + 2L * L * n,
                               a->tau + 2L * L * n, a->vh + 2L * L * nn, a->tri_work_s, ss));

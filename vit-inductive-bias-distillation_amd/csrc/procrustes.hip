@@ -1716,24 +1716,8 @@ int basd_procrustes_finalize(const float* w, long w_batch_stride, const float* s
     BASD_RETURN_LAST();
 }
 
-// Gradient of sum_b coef * loss_b with respect to the student tokens (autograd of relational.py:36-50).
-int basd_student_grad(const void* x, int dtype, long sb, long sn, int B, int n_s, int n_t, int D, const float* omega,
-                      const float* mu, const float* h, const int* tap0, const int* tap1, const float* lam,
-                      const float* scale_ptr, float scale_const, float* dx, const float* tnorm2, float* gomega,
-                      hipStream_t stream) {
-    BASD_CHECK_ARG(x && omega && mu && h && scale_ptr && dx && B > 0 && n_s > 0 && n_t > 0 && D > 0);
-    BASD_CHECK_ARG((gomega == nullptr) || (tnorm2 != nullptr));
-    const dim3 grid(n_s, B);
-    if (dtype == BASD_DTYPE_F32)
-        student_grad_kernel<float><<<grid, 128, 0, stream>>>((const float*)x, nullptr, sb, sn, n_s, n_t, D, omega, 0, mu, h, tap0, tap1, lam, scale_ptr, scale_const, dx, tnorm2, gomega);
-    else if (dtype == BASD_DTYPE_BF16)
-        student_grad_kernel<__hip_bfloat16><<<grid, 128, 0, stream>>>((const __hip_bfloat16*)x, nullptr, sb, sn, n_s, n_t, D, omega, 0, mu, h, tap0, tap1, lam, scale_ptr, scale_const, dx, tnorm2, gomega);
-    else
-        return BASD_EINVAL;
-    BASD_RETURN_LAST();
-}
-
-// The same for all E extraction layers in one launch: x_ptrs device table of E base pointers (common strides),
+// Gradient of sum_b coef * loss_b with respect to the student tokens (autograd of relational.py:36-50), for all E
+// extraction layers in one launch: x_ptrs device table of E base pointers (common strides),
 // omega + e * omega_e_stride (0: one weight vector for all layers), mu / h / dx / tnorm2 / gomega laid out (E, B, ...),
 // scale_ptr[e] the upstream gradient of layer e.
 int basd_student_grad_multi(const void* const* x_ptrs, int dtype, long sb, long sn, int E, int B, int n_s, int n_t,
