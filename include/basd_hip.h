@@ -702,6 +702,30 @@ int basd_mix_batch(const void* src, int src_dtype, void* dst, int dst_dtype, int
                    const float* std /* host */, const long* labels, int K, double lam_targets, float* targets,
                    hipStream_t stream);
 
+/* ---- teacher attention importance from the qkv projection's output in one launch ----------------------- */
+
+#define BASD_ATTN_CLS_ROW 0
+#define BASD_ATTN_QUERY_MEAN 1
+
+/* replaces: the attention hook `qkv = mod.qkv(x).reshape(B, N, 3, nh, hd).permute(2, 0, 3, 1, 4);
+ *           attn = (q @ k.transpose(-2, -1)) * scale; attn.softmax(dim=-1)`  src/models/teacher.py:27-39, reduced to
+ *           what the loss reads of it, `attn.mean(dim=1)[:, 0, 1:]` / `attn.mean(dim=1).mean(dim=1)`
+ *           src/losses/relational.py:22-27 (the mean over heads stays with the loss: layer mixing comes first).
+ * qkv: the OUTPUT of a fused projection, (B, N, 3 H hd) fp32 / bf16, last axis laid out [3][H][hd] with unit stride;
+ * batch / token strides sb / sn (elements) are arbitrary: a view is read in place (16-byte loads where its address and
+ * strides allow, element loads otherwise).  out: dense (B, H, N) fp32, written whole.
+ *   mode BASD_ATTN_CLS_ROW:     out[b,h,j] = softmax_j(scale q[b,h,0] . k[b,h,j])          (all N columns)
+ *   mode BASD_ATTN_QUERY_MEAN:  out[b,h,j] = (1/N) sum_i softmax_j(scale q[b,h,i] . k[b,h,j])
+ * Q K^T runs on the matrix cores (bf16 input: v_mfma_f32_32x32x16_bf16, fp32 input: v_mfma_f32_32x32x2_f32, the
+ * contraction padded with zeros), fp32 accumulation, fp32 softmax with the row maximum subtracted; the score tiles
+ * are recomputed in a second pass over the keys, so nothing of size N^2 is written to memory.  Fixed-order
+ * reductions, no atomics: the bits depend on the arguments only.  A NaN or +inf score makes out[b,h,:] of its own
+ * (b, h) NaN and nothing else; large finite scores do not overflow.
+ * Supported: 1 <= N <= 1025, hd a multiple of 8 up to 128, any B, H >= 1; anything else returns BASD_EUNSUPPORTED
+ * before anything is launched.  ONE launch, no workspace, nothing the caller must zero. */
+int basd_attn_importance(const void* qkv, int dtype, long sb, long sn, int B, int N, int H, int hd, int mode,
+                         float scale, float* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,9 @@
 """A real DeiT-S <- ResNet-50 distillation step at batch 256 (stock torch models, random init, synthetic images) around
 the HIP loss path: time of the whole step and of its parts, so that the share of the loss is a measured number.
 usage: trainer_step_bench.py [--batch 256] [--steps 8] [--dtype bf16|fp32] [--optimizer adamw|schedulefree]
-[--mixup torch|fused]  (torch: the op chain of trainer.mixup_cutmix; fused: basd_amd.augment, one launch per batch)"""
+[--mixup torch|fused]  (torch: the op chain of trainer.mixup_cutmix; fused: basd_amd.augment, one launch per batch)
+[--teacher resnet50|vit_b] [--attn-capture torch|fused]  (vit_b: a ViT-B/16 teacher, 12 hooked attention layers;
+fused: basd_amd.attention on each block's own qkv output, one launch per layer)"""
 import argparse, os, sys, time
 from types import SimpleNamespace
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,17 +19,23 @@ ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--dtype", default="bf16")
 ap.add_argument("--optimizer", default="adamw", choices=["adamw", "schedulefree"])
 ap.add_argument("--mixup", default="torch", choices=["torch", "fused"])
+ap.add_argument("--teacher", default="resnet50", choices=["resnet50", "vit_b"])
+ap.add_argument("--attn-capture", default="torch", choices=["torch", "fused"])
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 student = SM.StockViT().to(dev)                      # DeiT-S
-teacher = SM.make_teacher(SM.StockResNet().to(dev), 224)
+if args.teacher == "vit_b":
+    teacher = SM.make_teacher(SM.StockViT(embed_dim=768, depth=12, num_heads=12, num_classes=0).to(dev), 224)
+else:
+    teacher = SM.make_teacher(SM.StockResNet().to(dev), 224)
 cfg = SimpleNamespace(training=SimpleNamespace(label_smoothing=0.1, learning_rate=1e-3, weight_decay=0.05),
                       basd=SimpleNamespace(num_extraction_points=4), model=SimpleNamespace(num_classes=1000))
 torch.manual_seed(42)
 ac = torch.bfloat16 if args.dtype == "bf16" else None
 tr = T.Trainer(student, cfg, teacher, student_info=SM.probe_model(student, 224), autocast_dtype=ac,
-               mixup=True if args.mixup == "torch" else "fused", optimizer=args.optimizer)
+               mixup=True if args.mixup == "torch" else "fused", optimizer=args.optimizer,
+               attn_capture=args.attn_capture)
 g = torch.Generator().manual_seed(1)
 B = args.batch
 # images with per-image structure (a random colour cast + noise) so that the teacher features are not pure noise
@@ -58,7 +66,7 @@ def fwd_student():
 
 def fwd_teacher():
     with acx:
-        return capture.extract_intermediates(teacher, batch["clean"])
+        return capture.extract_intermediates(teacher, batch["clean"], attn=args.attn_capture)
 
 
 with torch.no_grad():
@@ -77,6 +85,7 @@ def loss_only():
 
 loss_only()
 l_ms = timed(loss_only, args.steps)
-print({"batch": B, "dtype": args.dtype, "optimizer": args.optimizer, "mixup": args.mixup, "step_ms": round(step_ms, 2), "images_per_s": round(B / step_ms * 1e3, 1),
+print({"batch": B, "dtype": args.dtype, "optimizer": args.optimizer, "mixup": args.mixup, "teacher": args.teacher,
+       "attn_capture": args.attn_capture, "step_ms": round(step_ms, 2), "images_per_s": round(B / step_ms * 1e3, 1),
        "student_fwd_nograd_ms": round(s_ms, 2), "teacher_fwd_ms": round(t_ms, 2), "loss_fwd_bwd_ms": round(l_ms, 2),
        "loss_share": round(l_ms / step_ms, 3), "loss": float(out["loss"]), "ranks": dict(tr.basd_loss.layer_selector.subspace_ranks)})

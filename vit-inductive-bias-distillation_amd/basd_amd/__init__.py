@@ -10,6 +10,12 @@ Sub-modules:
   ``evaluation``  ``evaluate_model`` / ``EvalAccumulator``: top-1 / top-5 and loss, one launch per validation batch
   ``augment``  ``BatchMixer`` / ``draw_mix_params``: MixUp / CutMix, soft targets and the uint8 conversion, one launch
                per batch
+  ``attention``  ``attn_importance``: a teacher's attention importance (CLS row / mean over queries) from the output of
+               its own ``qkv`` projection, one launch per layer
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
 __version__ = "0.1.0"
+
+from .attention import attn_importance  # noqa: E402
+
+__all__ = ["attn_importance"]

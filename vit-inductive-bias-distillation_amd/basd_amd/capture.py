@@ -10,7 +10,10 @@ maintainer swaps the import and nothing else.  What differs is what is materiali
   ``attn[:, :, 0, 1:]`` and nothing else of a ViT teacher's maps (relational.py:23-24) -- and returns it as a
   (B, H, N, N) view with a zero stride along the query axis: B*H*N floats per layer instead of B*H*N^2
   (cfg-4: 38.5 MB instead of 7.6 GB per step);
-* ``estimate_intrinsic_dim`` runs the Marchenko-Pastur rank on the GPU library (no CPU eigvalsh of a D_t x D_t Gram).
+* ``estimate_intrinsic_dim`` runs the Marchenko-Pastur rank on the GPU library (no CPU eigvalsh of a D_t x D_t Gram);
+* ``make_qkv_importance_hook`` / ``extract_intermediates(..., attn="fused")`` hook the block's own ``qkv`` Linear and
+  reduce its OUTPUT to the importance the loss reads (CLS row, or the mean over queries for a teacher without a CLS
+  token) in one launch of ``basd_amd.attention.attn_importance``: no second projection, no N x N map in either case.
 
 Only torch module plumbing lives here (hooks, views, one Linear slice per hooked attention block); no kernels.
 """
@@ -22,10 +25,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .attention import attn_importance
 from .losses import marchenko_pastur_rank
 
-__all__ = ["make_attn_capture_hook", "_to_token_format", "estimate_intrinsic_dim", "extract_intermediates",
-           "_extract_student", "_derive_from_teacher"]
+__all__ = ["make_attn_capture_hook", "make_qkv_importance_hook", "_to_token_format", "estimate_intrinsic_dim",
+           "extract_intermediates", "_extract_student", "_derive_from_teacher"]
 
 
 # reference src/models/teacher.py:27-39
@@ -51,6 +55,21 @@ def make_attn_capture_hook(capture_dict: dict, layer_idx: int, *, apply_softmax:
         row = (q @ k.transpose(-2, -1)) * (hd ** -0.5)                     # (B, nh, 1, N)
         row = row.softmax(dim=-1) if apply_softmax else row
         capture_dict[layer_idx] = row.expand(B, nh, N, N)                  # zero stride along the query axis
+
+    return hook
+
+
+def make_qkv_importance_hook(capture_dict: dict, layer_idx: int, num_heads: int, *, mode: str):
+    """Forward hook for the ``qkv`` Linear of a timm-style attention module (output (B, N, 3 * num_heads * hd), last axis
+    ``[3][num_heads][hd]`` as the reference hook's ``reshape(B, N, 3, nh, hd)`` assumes).  ``mode``: ``"cls_row"`` or
+    ``"query_mean"`` (``basd_amd.attention``).  Stores the (B, H, N) importance as a (B, H, N, N) view with a zero
+    stride along the query axis: what the CLS-row hook above hands to the loss.  Like the reference hook it ignores any
+    ``q_norm`` / ``k_norm`` of the attention module.  GPU only."""
+
+    def hook(mod, inp, out):
+        imp = attn_importance(out, num_heads, mode=mode)                   # (B, H, N) fp32, one launch
+        B, H, N = imp.shape
+        capture_dict[layer_idx] = imp[:, :, None, :].expand(B, H, N, N)
 
     return hook
 
@@ -83,8 +102,12 @@ def estimate_intrinsic_dim(teacher, images: torch.Tensor) -> int:
 
 # reference src/models/teacher.py:180-215
 @torch.no_grad()
-def extract_intermediates(teacher, x: torch.Tensor, *, cls_row_only: bool = True):
-    """(tokens per layer, attention per layer) as ``BASDLoss.forward`` expects them."""
+def extract_intermediates(teacher, x: torch.Tensor, *, cls_row_only: bool = True, attn: str = "torch"):
+    """(tokens per layer, attention per layer) as ``BASDLoss.forward`` expects them.  ``attn="torch"``: the attention
+    module's hook above; ``attn="fused"`` (GPU only): ``make_qkv_importance_hook`` on each hooked block's ``qkv`` Linear,
+    the CLS row for a teacher with a CLS token, the mean over queries otherwise (``cls_row_only`` is not consulted)."""
+    if attn not in ("torch", "fused"):
+        raise ValueError(f"attn must be 'torch' or 'fused', not {attn!r}")
     if teacher.feature_format != "token":
         features = teacher.model.forward_features(x)
         features = _to_token_format(features, teacher.feature_format, teacher.has_cls_token)
@@ -101,13 +124,21 @@ def extract_intermediates(teacher, x: torch.Tensor, *, cls_row_only: bool = True
                 captured_tokens[i] = _to_token_format(out, teacher.feature_format, teacher.has_cls_token)
             return hook
         hooks.append(module.register_forward_hook(make_token_hook(idx)))
-        if teacher.attn_subpath is not None:
+        if teacher.attn_subpath is not None and attn == "fused":
+            attn_mod = teacher.model.get_submodule(f"{path}.{teacher.attn_subpath}")
+            qkv_mod = teacher.model.get_submodule(f"{path}.{teacher.attn_subpath}.qkv")
+            hooks.append(qkv_mod.register_forward_hook(make_qkv_importance_hook(
+                captured_attns, idx, attn_mod.num_heads,
+                mode="cls_row" if teacher.has_cls_token else "query_mean")))
+        elif teacher.attn_subpath is not None:
             attn_mod = teacher.model.get_submodule(f"{path}.{teacher.attn_subpath}")
             hooks.append(attn_mod.register_forward_hook(make_attn_capture_hook(
                 captured_attns, idx, apply_softmax=True, cls_row_only=cls_row_only and teacher.has_cls_token)))
-    teacher.model(x)
-    for h in hooks:
-        h.remove()
+    try:
+        teacher.model(x)
+    finally:
+        for h in hooks:
+            h.remove()
     return captured_tokens, captured_attns
 
 

@@ -89,10 +89,14 @@ class Trainer:
     (mean, std)}`` per channel; with it (and ``mixup="fused"``) the loader may hand over uint8 batches: ``augmented`` is
     normalised inside the mixing launch, ``clean`` by a convert-only launch with the teacher's statistics.  A uint8 batch
     without it, or with another ``mixup``, raises ``TypeError``.  ``mix_dtype``: dtype the fused launches write
-    (``torch.bfloat16``: what autocast would cast the images to anyway; default: fp32 for uint8, else the batch's own)."""
+    (``torch.bfloat16``: what autocast would cast the images to anyway; default: fp32 for uint8, else the batch's own).
+    ``attn_capture``: ``"torch"`` (the capture hooks of ``basd_amd.capture`` with torch ops) or ``"fused"`` (the teacher's
+    attention importance from the output of each hooked block's own ``qkv`` Linear, one HIP launch per layer,
+    ``basd_amd.attention``; GPU only)."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
-                 autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None) -> None:
+                 autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
+                 attn_capture: str = "torch") -> None:
         self.config = config
         self.device = next(student_model.parameters()).device
         self.criterion = nn.CrossEntropyLoss(label_smoothing=config.training.label_smoothing)
@@ -122,6 +126,9 @@ class Trainer:
         if mixup not in (True, False, "fused"):
             raise ValueError(f"mixup must be True, False or 'fused', not {mixup!r}")
         self.mixup = mixup
+        if attn_capture not in ("torch", "fused"):
+            raise ValueError(f"attn_capture must be 'torch' or 'fused', not {attn_capture!r}")
+        self.attn_capture = attn_capture
         self.image_stats = image_stats
         self._mixer = self._clean_mixer = None
         if image_stats is not None and set(image_stats) != {"clean", "augmented"}:
@@ -182,7 +189,7 @@ class Trainer:
             logits, s_tokens = capture._extract_student(self.model, student_imgs, self.basd_loss.token_layers,
                                                         layer_paths=self._student_layer_paths,
                                                         has_cls_token=self._student_has_cls)
-            teacher_tokens, teacher_attns = capture.extract_intermediates(self._teacher, clean)
+            teacher_tokens, teacher_attns = capture.extract_intermediates(self._teacher, clean, attn=self.attn_capture)
         # the loss is computed outside autocast: fp32 logits, tokens consumed in their own dtype (fp32 internal)
         loss = self.basd_loss(logits.float(), mixed_targets, s_tokens, teacher_tokens, teacher_attns)
         loss.backward()
