@@ -726,6 +726,32 @@ int basd_mix_batch(const void* src, int src_dtype, void* dst, int dst_dtype, int
 int basd_attn_importance(const void* qkv, int dtype, long sb, long sn, int B, int N, int H, int hd, int mode,
                          float scale, float* out, hipStream_t stream);
 
+/* ---- dataset statistics: exact per-channel sums of uint8 pixels in one launch -------------------------- */
+
+#define BASD_LAYOUT_HWC 0
+#define BASD_LAYOUT_CHW 1
+
+/* replaces: the body of the image loop of `get_channel_stats`  src/data/datasets.py:46-68 -- the conversion of every
+ *           image to float64 on the host, its per-image `mean` / `var`, and the running merge of those.
+ * src: uint8, dense, at ANY byte address (callers pass views):
+ *   layout BASD_LAYOUT_HWC: images * pixels pixels of C interleaved bytes (`np.asarray(pil_image)`, a stack of such
+ *                           arrays, or any concatenation of ragged images cut at pixel boundaries);
+ *   layout BASD_LAYOUT_CHW: images * C planes of `pixels` bytes each (a dense NCHW batch).
+ * 1 <= C <= 4.  state: 9 words on the device, ADDED to by 64-bit integer atomic adds (agent scope; zero them to start):
+ *   state[0] += images * pixels;   state[1 + c] += sum of x over channel c;   state[5 + c] += sum of x^2 over channel c
+ * for c < C; the words of channels >= C are not touched.  The sums are integers and are exact, so the state is the same
+ * bits whatever the order of arrival, the launch geometry, the cutting of the data into calls or their number; per
+ * channel there is room for 2^63 / 255^2 > 1.4e14 pixels.  Mean and standard deviation are the caller's to form
+ * (basd_amd.stats.finish: exact rational arithmetic, rounded once).
+ * 16-byte loads behind a head of single bytes up to the first 16-byte boundary (of every plane, in CHW); both sums of
+ * a dword by v_dot4_u32_u8.  ONE launch, no memset, no workspace, no copy; at most nine atomic adds per workgroup.
+ * images * pixels == 0 launches nothing and returns 0; C outside 1..4, an unknown layout, a negative size, more than
+ * 2^40 pixels in one call or more than 2^31 tiles of 3 KiB return BASD_EINVAL before anything is launched.
+ * max_blocks: test / tuning hook; 0 = the entry point chooses the grid, > 0 = a cap on its workgroups (the result does
+ * not depend on it). */
+int basd_channel_stats(const unsigned char* src, int layout, long images, int C, long pixels, long long* state,
+                       int max_blocks, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

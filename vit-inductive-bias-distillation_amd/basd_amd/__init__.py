@@ -12,6 +12,7 @@ Sub-modules:
                per batch
   ``attention``  ``attn_importance``: a teacher's attention importance (CLS row / mean over queries) from the output of
                its own ``qkv`` projection, one launch per layer
+  ``stats``    ``channel_stats`` / ``ChannelStats``: exact per-channel mean and std of uint8 images, one launch per chunk
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
 __version__ = "0.1.0"

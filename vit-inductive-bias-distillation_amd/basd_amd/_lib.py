@@ -115,6 +115,7 @@ SIGNATURES = {
     "basd_mix_batch": [vp, i32, vp, i32, i32, i32, i32, i32, i32, f64, i32, i32, i32, i32, vp, vp, vp, i32, f64, vp,
                        vp],
     "basd_attn_importance": [vp, i32, i64, i64, i32, i32, i32, i32, i32, f32, vp, vp],
+    "basd_channel_stats": [vp, i32, i64, i32, i64, vp, i32, vp],
 }
 
 class ProcrustesArgs(C.Structure):

@@ -111,19 +111,35 @@ def _label_smoothing_of(criterion) -> float:
 
 @torch.no_grad()
 def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_classes: int, valid_indices=None,
-                   distributed: bool = False) -> dict:
+                   distributed: bool = False, image_stats=None, input_dtype=None) -> dict:
     """The reference's ``evaluate_model``: batches are dicts with ``pixel_values`` and ``label``; returns ``val_acc``,
     ``val_acc_top5`` (percent) and ``loss`` (mean of ``criterion`` over the samples); fewer than 5 evaluated classes
     raise ``ValueError``.  ``distributed=True``: every rank iterates its own shard and the counts are summed over the
-    default process group before they are read."""
+    default process group before they are read.
+    ``image_stats``: ``(mean, std)`` per channel; with it the loader may hand over uint8 ``pixel_values`` (a
+    ``ToImage()``-only pipeline): they are scaled and normalised on the device by one convert-only launch of
+    ``basd_amd.augment.BatchMixer`` (``MixParams("none")``) that writes ``input_dtype`` (default fp32).  A uint8 batch
+    without ``image_stats`` raises ``TypeError`` before the model sees it.  Float batches go to the model as they are,
+    whatever ``image_stats`` and ``input_dtype`` say."""
     label_smoothing = _label_smoothing_of(criterion)
     model.eval()
     device = next(model.parameters()).device
     acc = EvalAccumulator(num_classes, valid_indices=valid_indices, label_smoothing=label_smoothing, top_k=5,
                           device=device)
+    converter = None
+    if image_stats is not None:
+        from .augment import BatchMixer, MixParams
+        mean, std = image_stats
+        converter = BatchMixer(num_classes, mean=mean, std=std, out_dtype=input_dtype, device=device)
     for batch in data_loader:
-        inputs = batch["pixel_values"].to(device, non_blocking=True)
+        inputs = batch["pixel_values"]
+        if inputs.dtype == torch.uint8 and converter is None:
+            raise TypeError("uint8 pixel_values need image_stats=(mean, std): the conversion and the normalisation run "
+                            f"on the device; got {inputs.dtype} of shape {tuple(inputs.shape)} and image_stats=None")
+        inputs = inputs.to(device, non_blocking=True)
         targets = batch["label"].to(device, non_blocking=True)
+        if inputs.dtype == torch.uint8:
+            inputs, _ = converter(inputs, None, MixParams("none"))
         acc.update(model(inputs), targets)
     if distributed:
         acc.all_reduce()

@@ -130,6 +130,7 @@ class Trainer:
             raise ValueError(f"attn_capture must be 'torch' or 'fused', not {attn_capture!r}")
         self.attn_capture = attn_capture
         self.image_stats = image_stats
+        self.mix_dtype = mix_dtype
         self._mixer = self._clean_mixer = None
         if image_stats is not None and set(image_stats) != {"clean", "augmented"}:
             raise ValueError(f"image_stats needs the keys 'clean' and 'augmented' (got {sorted(image_stats)})")
@@ -254,12 +255,16 @@ class Trainer:
     def evaluate(self, model: nn.Module, val_loader) -> dict:
         """The reference's validation call (trainer.py:185-189): ``evaluate_model`` with the trainer's smoothed
         criterion -- one HIP launch per batch, one read-back per epoch; over the ranks' shards when a process group
-        with more than one rank exists.  Has the signature ``train(..., evaluate=)`` expects:
-        ``trainer.train(train_loader, val_loader, evaluate=trainer.evaluate)``."""
+        with more than one rank exists.  With ``image_stats`` the validation loader may hand over uint8
+        ``pixel_values``: they are normalised on the device with the ``augmented`` statistics -- the dataset's own, which
+        the reference's validation loader uses too (datasets.py:168-175) -- and written as ``mix_dtype``.  Has the
+        signature ``train(..., evaluate=)`` expects: ``trainer.train(train_loader, val_loader,
+        evaluate=trainer.evaluate)``."""
         from .evaluation import evaluate_model
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        stats = None if self.image_stats is None else self.image_stats["augmented"]
         return evaluate_model(model, val_loader, self.criterion, num_classes=self.config.model.num_classes,
-                              distributed=distributed)
+                              distributed=distributed, image_stats=stats, input_dtype=self.mix_dtype)
 
     def train(self, train_loader, val_loader=None, start_epoch: int = 0, *, evaluate=None, on_epoch_end=None) -> dict:
         """The reference's epoch loop (trainer.py:171-216): ``_train_epoch``, validation, ``metrics_history``,
