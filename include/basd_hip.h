@@ -13,7 +13,8 @@
  *   - dtype codes: 0 = fp32, 1 = bf16 (inputs only; all arithmetic and outputs are fp32/fp64), 2 = uint8 (image
  *     batches of basd_mix_batch only, which is also the one entry point that may write bf16);
  *   - entry points are re-entrant and keep no global mutable state, with a few process-wide test / tuning hooks as the
- *     only exceptions: basd_tridiag_tuning, basd_jacobi_tuning, basd_jacobi_ordering, basd_gemm_tuning, basd_procrustes_tuning (none is called by the
+ *     only exceptions: basd_tridiag_tuning, basd_jacobi_tuning, basd_jacobi_ordering, basd_gemm_tuning, basd_procrustes_tuning,
+ *     basd_procrustes_finish_tuning (none is called by the
  *     loss), and the launch counter behind basd_sfadamw_launches (diagnostics).
  */
 #ifndef BASD_HIP_H
@@ -458,7 +459,8 @@ int basd_student_grad_fused(const void* const* x_ptrs, int dtype, long sb, long 
 /* The whole forward of relational.py:22-50 for E extraction layers against the (mixed) teacher -- and, when `dx` is
  * set, the student-token gradients for the upstream gradients `grad_layers` -- queued by ONE call: the launches of
  * basd_token_weights, basd_teacher_center, basd_student_project(_multi), basd_gram_f64 x2, basd_chol_f64,
- * basd_stack_product, basd_jacobi_onesided, basd_procrustes_finalize [, basd_student_grad_fused or basd_gemm_tn + basd_student_grad_multi] in
+ * basd_stack_product, basd_jacobi_onesided, basd_procrustes_finalize (transposed cores of n <= 64 with k_prime set:
+ * basd_procrustes_finish_transposed) [, basd_student_grad_fused or basd_gemm_tn + basd_student_grad_multi] in
  * that order (a dozen FFI calls from Python cost several times the launches themselves, and that host time sat in
  * front of the caller's stream).  All fields are 8 bytes wide; pointers are device memory except student_host_ptrs.
  *   G = 1: the teacher side is shared by all layers (one teacher layer: mixing weights exactly 1), else G = E.
@@ -514,6 +516,21 @@ int basd_stack_product_t(const double* la, const double* lb, long l_batch_stride
 int basd_kprime_from_transposed(const float* w, long w_batch_stride, const float* sigma, int n, int batch,
                                 const double* lb, long l_batch_stride, int lb_period, float* z, long z_batch_stride,
                                 float* k_prime, hipStream_t stream);
+/* relational.py:47-50 behind the Jacobi of the transposed route for cores of n <= 64 tokens, in ONE launch: the
+ * per-sample terms of basd_procrustes_finalize (called with k_prime == NULL) and the K' of basd_kprime_from_transposed,
+ * bit for bit (same reduction order, every sum one fmaf per term in ascending order), with X = V Sigma and L_b read
+ * once and Z kept on chip: no z buffer.  Arguments as in those two.  Returns BASD_EUNSUPPORTED without launching for
+ * n > 64 or batch > 65535: call the two. */
+int basd_procrustes_finish_transposed(const float* w, long w_batch_stride, const float* sigma, int n, int n_s,
+                                      int batch, int t_period /* gb, omega indexed by b % t_period */,
+                                      const double* gb, long g_batch_stride, const float* omega, const int* tap0,
+                                      const int* tap1, const float* lam, const float* tr_s_part, int tr_slabs,
+                                      float* tr_s, float* tr_t, float* nuc, float* loss, const double* lb,
+                                      long l_batch_stride, int lb_period, float* k_prime, hipStream_t stream);
+/* Test / measurement hook of basd_procrustes_forward_fused: 1 (default) = basd_procrustes_finish_transposed where it
+ * applies, 0 = always basd_procrustes_finalize + basd_kprime_from_transposed; negative = query only.  Returns the
+ * previous setting (not a status).  Process-wide. */
+int basd_procrustes_finish_tuning(int fused);
 /* The transposed route for steps whose backward goes through the mixing weights (multi-layer teachers; autograd of
  * relational.py:47-48 w.r.t. the teacher side reads U Sigma, the top half of the stacked cores: basd_teacher_factor*):
  * basd_ustack_stash, between basd_stack_product_t and the Jacobi, copies M (row-major, compact at wc) into the unused

@@ -82,6 +82,9 @@ SIGNATURES = {
     "basd_jacobi_plain4_fits": [i32],
     "basd_stack_product_t": [vp, vp, i64, i32, i32, i32, vp, i64, vp],
     "basd_kprime_from_transposed": [vp, i64, vp, i32, i32, vp, i64, i32, vp, i64, vp, vp],
+    "basd_procrustes_finish_transposed": [vp, i64, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                          vp, vp, i64, i32, vp, vp],
+    "basd_procrustes_finish_tuning": [i32],
     "basd_ustack_stash": [vp, i64, i32, i32, vp, i64, vp],
     "basd_ustack_from_transposed": [vp, i64, vp, i32, i32, vp, i64, vp, i64, vp, i32, vp, vp],
     "basd_resample_tokens": [vp, i32, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp],

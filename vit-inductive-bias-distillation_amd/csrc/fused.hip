@@ -108,6 +108,14 @@ int basd_procrustes_tuning(int transposed_cores) {
     if (transposed_cores >= 0) g_transposed_cores = transposed_cores > 2 ? 2 : transposed_cores;
     return BASD_OK;
 }
+// Test / measurement hook: 0 keeps basd_procrustes_finalize + basd_kprime_from_transposed behind the transposed route's
+// Jacobi, 1 (default) takes basd_procrustes_finish_transposed where it applies.  Returns the previous setting.
+static int g_finish_fused = 1;
+int basd_procrustes_finish_tuning(int fused) {
+    const int prev = g_finish_fused;
+    if (fused >= 0) g_finish_fused = fused ? 1 : 0;
+    return prev;
+}
 
 // relational.py:22-50 for all extraction layers against the (mixed) teacher, forward and -- optionally -- the student
 // gradients for given upstream gradients; see BasdProcrustesArgs in include/basd_hip.h.
@@ -186,12 +194,23 @@ int basd_procrustes_forward_fused(const BasdProcrustesArgs* a, hipStream_t st) {
         if (a->raw != nullptr) BASD_TRY(basd_ustack_stash(a->W, 2 * nn, n, EB, a->w_stack, 2 * nn, st));
         BASD_TRY(basd_jacobi_onesided(a->W, 2 * nn, n, n, n, EB, nullptr, a->sigma, n, (int)a->max_sweeps, 0.f,
                                       a->jflags, a->sweeps, st));
-        BASD_TRY(basd_procrustes_finalize(a->W, 2 * nn, a->sigma, n, n_s, EB, GB, a->g_all + (long)EB * nn, nn, a->omega,
-                                          a->tap0, a->tap1, a->lam, a->tr_part, slabs, a->tr_s, a->tr_t, a->nuc,
-                                          a->loss_b, nullptr, st));
-        if (a->k_prime)
-            BASD_TRY(basd_kprime_from_transposed(a->W, 2 * nn, a->sigma, n, EB, a->l_all + (long)EB * nn, nn, GB,
-                                                 a->W + nn, 2 * nn, a->k_prime, st));
+        // cores of up to 64 tokens: the per-sample terms and K' in one launch, same bits (see the kernel)
+        rc = BASD_EUNSUPPORTED;
+        if (a->k_prime && g_finish_fused)
+            rc = basd_procrustes_finish_transposed(a->W, 2 * nn, a->sigma, n, n_s, EB, GB, a->g_all + (long)EB * nn, nn,
+                                                   a->omega, a->tap0, a->tap1, a->lam, a->tr_part, slabs, a->tr_s,
+                                                   a->tr_t, a->nuc, a->loss_b, a->l_all + (long)EB * nn, nn, GB,
+                                                   a->k_prime, st);
+        if (rc == BASD_EUNSUPPORTED) {
+            BASD_TRY(basd_procrustes_finalize(a->W, 2 * nn, a->sigma, n, n_s, EB, GB, a->g_all + (long)EB * nn, nn,
+                                              a->omega, a->tap0, a->tap1, a->lam, a->tr_part, slabs, a->tr_s, a->tr_t,
+                                              a->nuc, a->loss_b, nullptr, st));
+            if (a->k_prime)
+                BASD_TRY(basd_kprime_from_transposed(a->W, 2 * nn, a->sigma, n, EB, a->l_all + (long)EB * nn, nn, GB,
+                                                     a->W + nn, 2 * nn, a->k_prime, st));
+        } else if (rc != BASD_OK) {
+            return rc;
+        }
         if (a->raw != nullptr) {
             BASD_CHECK_ARG(a->sigma_u != nullptr);
             // (scratch: the z region behind X, free again once K' has been formed)

@@ -1145,6 +1145,152 @@ __global__ void __launch_bounds__(256) procrustes_finalize_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// The transposed route behind the Jacobi for cores of n <= 64 in ONE launch: what procrustes_finalize_kernel (Kp ==
+// nullptr), kprime_z_kernel and kprime_from_z_kernel do in three, bit for bit.  grid = batch, block = 256.
+// The per-sample terms are those of procrustes_finalize_kernel with the same thread-to-element assignment (same
+// reduction order).  X = V Sigma and the lower triangle of L_b (narrowed to fp32) are staged in LDS once, Z stays in
+// LDS, and every sum of Z and K' advances one fmaf per term with its index ascending from 0 and the scale applied once
+// after it -- the order of the tiled kernels, whose zero-padded terms leave an fp32 accumulator as it is.
+// LDS: three NP x ld arrays (NP = n rounded up to 4; ld = NP, or NP + 4 where NP / 4 is even, so that ld / 4 is odd and
+// rows ld apart start in different 16-byte bank slots), pads zero-filled; 32.5 KB at n = 49, 52 KB at n = 64.
+// Thread tid < (NP/4)^2 owns a 4 x 4 block of each product:
+//   Z:  columns c = ct + j NP/4 (strided: the 16 lanes of a ds_read_b128 group read 16 different slots of X),
+//       rows a = 4 at + i; r runs in float4 steps up to the block's own diagonal, L_b's zeros cover the rest
+//   K': rows 4 at + i, columns 4 bt + k; one float4 of Z per side and c
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) procrustes_finish_t_kernel(
+    const float* __restrict__ W, long w_batch_stride, const float* __restrict__ sigma, int n, int n_s,
+    const double* __restrict__ Gb, long g_batch_stride, const float* __restrict__ omega,
+    const int* __restrict__ tap0, const int* __restrict__ tap1, const float* __restrict__ lam,
+    const float* __restrict__ tr_s, int tr_slabs, float* __restrict__ tr_s_out, float* __restrict__ tr_t_out,
+    float* __restrict__ nuc_out, float* __restrict__ loss_out, int t_period,
+    const double* __restrict__ Lb, long l_batch_stride, int lb_period, float* __restrict__ Kp) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float red[32];
+    __shared__ double redd[32];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nq = (n + 3) >> 2, NP = 4 * nq, ld = (nq & 1) ? NP : NP + 4;
+    float* Xs = sm;                        // Xs[c * ld + r] = X[r][c]
+    float* Ls = Xs + NP * ld;              // Ls[a * ld + r] = L_b[a][r], 0 for r > a
+    float* Zs = Ls + NP * ld;              // Zs[c * ld + a] = Z[c][a]
+    float* zsc = Zs + NP * ld;             // NP: sigma_c^-1.5, 0 when truncated
+    // staging first, every load of a thread issued before its first LDS store (one memory round trip, not one per
+    // row): lane = column, wave w takes the rows w + 4 k
+    const float* Wb = W + (long)b * w_batch_stride;
+    const double* L = Lb + (long)(b % lb_period) * l_batch_stride;
+    {
+        const int col = tid & 63, row0 = tid >> 6;
+        float xr[16], lr[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int row = row0 + 4 * k;
+            const bool in = row < n && col < n;
+            xr[k] = in ? Wb[(long)row * n + col] : 0.f;
+            lr[k] = (in && col <= row) ? (float)L[(long)row * n + col] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int row = row0 + 4 * k;
+            if (row < NP && col < NP) {
+                Xs[row * ld + col] = xr[k];
+                Ls[row * ld + col] = lr[k];
+            }
+        }
+    }
+    // ---- per-sample terms: procrustes_finalize_kernel's code
+    const float* sg = sigma + (long)b * n;
+    float smax = 0.f, ssum = 0.f;
+    for (int j = tid; j < n; j += 256) {
+        smax = fmaxf(smax, sg[j]);
+        ssum += sg[j];
+    }
+    smax = wave_max(smax);
+    __syncthreads();
+    if ((tid & 63) == 0) red[tid >> 6] = smax;
+    __syncthreads();
+    smax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float nuc = block_sum(ssum, red);
+    const float thr = smax * (float)n * 1.1920929e-7f;
+    for (int c = tid; c < NP; c += 256) {
+        const float sv = c < n ? sg[c] : 0.f;
+        zsc[c] = sv > thr ? 1.f / (sv * sqrtf(sv)) : 0.f;
+    }
+    // teacher trace on the student grid: sum_n w_n |sum_j I[n,j] tc_j|^2, from the fp64 Gram
+    const int bt = b % t_period;          // teacher-side sample (Gram, weights) shared by the extraction layers
+    const double* G = Gb + (long)bt * g_batch_stride;
+    double part = 0.;
+    for (int s = tid; s < n_s; s += 256) {
+        const double w = (double)omega[(long)bt * n_s + s];
+        if (tap0) {
+            const int i0 = tap0[s], i1 = tap1[s];
+            const double l1 = (double)lam[s], l0 = 1. - l1;
+            part += w * (l0 * l0 * G[(long)i0 * n + i0] + 2. * l0 * l1 * G[(long)i0 * n + i1] + l1 * l1 * G[(long)i1 * n + i1]);
+        } else {
+            part += w * G[(long)s * n + s];
+        }
+    }
+    const double trt = block_sum(part, redd);
+    if (tid == 0) {
+        float trs = 0.f;
+        for (int k = 0; k < tr_slabs; ++k) trs += tr_s[(long)b * tr_slabs + k];
+        tr_s_out[b] = trs;
+        tr_t_out[b] = (float)trt;
+        nuc_out[b] = nuc;
+        loss_out[b] = trs + (float)trt - 2.f * nuc;
+    }
+    __syncthreads();                       // Xs, Ls, zsc
+    const bool own = tid < nq * nq;
+    const int at = tid / nq, ct = tid - at * nq;      // ct doubles as the column block bt of K'
+    if (own) {
+        float acc[4][4] = {};
+        for (int r4 = 0; r4 <= at; ++r4) {
+            float4 xv[4], lv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xv[j] = *(const float4*)(Xs + (ct + j * nq) * ld + 4 * r4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) lv[i] = *(const float4*)(Ls + (4 * at + i) * ld + 4 * r4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    acc[j][i] = fmaf(lv[i].x, xv[j].x, acc[j][i]);
+                    acc[j][i] = fmaf(lv[i].y, xv[j].y, acc[j][i]);
+                    acc[j][i] = fmaf(lv[i].z, xv[j].z, acc[j][i]);
+                    acc[j][i] = fmaf(lv[i].w, xv[j].w, acc[j][i]);
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = ct + j * nq;
+            const float sc = zsc[c];
+            *(float4*)(Zs + c * ld + 4 * at) = make_float4(acc[j][0] * sc, acc[j][1] * sc, acc[j][2] * sc, acc[j][3] * sc);
+        }
+    }
+    __syncthreads();                       // Zs
+    if (own) {
+        float acc[4][4] = {};
+        for (int c = 0; c < n; ++c) {
+            const float4 za = *(const float4*)(Zs + c * ld + 4 * at);
+            const float4 zb = *(const float4*)(Zs + c * ld + 4 * ct);
+            const float av[4] = {za.x, za.y, za.z, za.w}, bv[4] = {zb.x, zb.y, zb.z, zb.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[i][k] = fmaf(av[i], bv[k], acc[i][k]);
+        }
+        float* K = Kp + (long)b * n * n;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int a = 4 * at + i, bb = 4 * ct + k;
+                // the tiled kernel pads c to a multiple of 32 with + 0 * 0 terms, which turn an accumulator of -0 into +0
+                if (a < n && bb < n) K[(long)a * n + bb] = (n & 31) ? acc[i][k] + 0.f : acc[i][k];
+            }
+    }
+}
+
 // K' = Y diag(sigma^+) Y^T for cores past the LDS-resident finalize kernel (n > 199): 32 x 32 output tiles.
 // grid = (ceil(n/32), ceil(n/32), batch), block = 256.  Same truncation rule as procrustes_finalize_kernel.
 __global__ void __launch_bounds__(256) kprime_tiled_kernel(const float* __restrict__ W, long w_batch_stride,
@@ -1713,6 +1859,24 @@ int basd_procrustes_finalize(const float* w, long w_batch_stride, const float* s
         const int nt = (n + 31) / 32;
         kprime_tiled_kernel<<<dim3(nt, nt, batch), 256, 0, stream>>>(w, w_batch_stride, sigma, n, k_prime);
     }
+    BASD_RETURN_LAST();
+}
+
+// relational.py:47-50 behind the Jacobi of the transposed route, cores of n <= 64: the per-sample terms of
+// basd_procrustes_finalize (k_prime == nullptr) and the K' of basd_kprime_from_transposed, same bits, in one launch and
+// without the z buffer.  BASD_EUNSUPPORTED (nothing launched) for larger cores or batch > 65535: call those two.
+int basd_procrustes_finish_transposed(const float* w, long w_batch_stride, const float* sigma, int n, int n_s,
+                                      int batch, int t_period, const double* gb, long g_batch_stride,
+                                      const float* omega, const int* tap0, const int* tap1, const float* lam,
+                                      const float* tr_s_part, int tr_slabs, float* tr_s, float* tr_t, float* nuc,
+                                      float* loss, const double* lb, long l_batch_stride, int lb_period,
+                                      float* k_prime, hipStream_t stream) {
+    BASD_CHECK_ARG(w && sigma && gb && omega && tr_s_part && tr_s && tr_t && nuc && loss && lb && k_prime && n > 0 &&
+                   batch > 0 && tr_slabs > 0 && t_period > 0 && lb_period > 0);
+    if (n > 64 || batch > 65535) return BASD_EUNSUPPORTED;
+    const int nq = (n + 3) / 4, np = 4 * nq, ld = (nq & 1) ? np : np + 4;
+    const size_t lds = sizeof(float) * (size_t)(3 * np * ld + np);      // <= 52480 bytes
+    procrustes_finish_t_kernel<<<batch, 256, lds, stream>>>(w, w_batch_stride, sigma, n, n_s, gb, g_batch_stride, omega, tap0, tap1, lam, tr_s_part, tr_slabs, tr_s, tr_t, nuc, loss, t_period, lb, l_batch_stride, lb_period, k_prime);
     BASD_RETURN_LAST();
 }
 
