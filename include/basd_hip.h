@@ -769,6 +769,78 @@ int basd_attn_importance(const void* qkv, int dtype, long sb, long sn, int B, in
 int basd_channel_stats(const unsigned char* src, int layout, long images, int C, long pixels, long long* state,
                        int max_blocks, hipStream_t stream);
 
+/* ---- TrivialAugmentWide and the horizontal flip of uint8 batches in one launch -------------------------- */
+
+#define BASD_TAUG_IDENTITY 0
+#define BASD_TAUG_SHEAR_X 1
+#define BASD_TAUG_SHEAR_Y 2
+#define BASD_TAUG_TRANSLATE_X 3
+#define BASD_TAUG_TRANSLATE_Y 4
+#define BASD_TAUG_ROTATE 5
+#define BASD_TAUG_BRIGHTNESS 6
+#define BASD_TAUG_COLOR 7
+#define BASD_TAUG_CONTRAST 8
+#define BASD_TAUG_SHARPNESS 9
+#define BASD_TAUG_POSTERIZE 10
+#define BASD_TAUG_SOLARIZE 11
+#define BASD_TAUG_AUTOCONTRAST 12
+#define BASD_TAUG_EQUALIZE 13
+
+/* Images of C*H*W bytes up to this are staged in LDS (3 x 224 x 224); larger ones are read from memory twice. */
+#define BASD_TAUG_STAGE_BYTES 150528
+
+/* One row of the device table, one per image (64 bytes). */
+typedef struct BasdTaugRecord {
+    int op;        /* BASD_TAUG_* */
+    int flip;      /* non-zero: every read of source pixel (y, x) below reads (y, W - 1 - x): the result is op(flip(image)) */
+    int iarg;      /* Posterize: bits */
+    float farg;    /* ops 6-9: f = 1 + m as fp32; Solarize: the threshold */
+    double a[6];   /* ops 0-5: the inverse affine map, made on the host */
+} BasdTaugRecord;
+
+/* replaces: `v2.RandomHorizontalFlip(), v2.TrivialAugmentWide()` of the training transform  src/data/datasets.py:137-144
+ *           (torchvision.transforms.v2; 31 magnitude bins, nearest interpolation, fill 0), which the reference runs per
+ *           image in Pillow inside its loader's workers.  Which op, which magnitude and whether to flip are the host's
+ *           draws (basd_amd.trivial_augment); they arrive as one BasdTaugRecord per image.
+ * src: dense NCHW (B, C, H, W) uint8, C in {1, 3}, at any byte address; dst: the same shape, not overlapping src
+ * (checked); table: B records on the device; status: one int on the device, OR-ed into (bit 0: a record with an op
+ * code outside the table; its image is copied, flipped if the record says so).  This text is the specification; the
+ * kernel equals it bit for bit, and it equals Pillow 12 (ImageEnhance, ImageOps, Image.transform, Image.rotate) bit for
+ * bit except for rotations at source coordinates within 1/256 of an integer (Pillow walks them in 16.16 fixed point).
+ *
+ * Ops 0-5 (Identity, ShearX, ShearY, TranslateX, TranslateY, Rotate): output pixel (x, y) takes the source pixel at
+ *   sx = floor(a0 (x + 0.5) + a1 (y + 0.5) + a2),  sy = floor(a3 (x + 0.5) + a4 (y + 0.5) + a5),
+ * evaluated in fp64 from left to right, every product and sum rounded on its own; 0 where (sx, sy) lies outside the
+ * image.  The host's matrices: Identity (1, 0, 0, 0, 1, 0); ShearX by m (1, m, 0, 0, 1, 0) (about the top-left corner,
+ * `center=[0, 0]`); ShearY by m (1, 0, 0, m, 1, 0); TranslateX by t = int(m) (1, 0, -t, 0, 1, 0); TranslateY by t
+ * (1, 0, 0, 0, 1, -t); Rotate by m degrees as PIL.Image.rotate: angle = m mod 360, r = -radians(angle), the matrix
+ * [cos r, sin r, 0, -sin r, cos r, 0] with every entry round(., 15), centre (W/2, H/2), a2 = (a0 (-cx) + a1 (-cy)) + cx
+ * and a5 likewise with cy; angle 0 is the identity; 180 is (-1, 0, W, 0, -1, H); on square images 90 is
+ * (0, -1, W, 1, 0, 0) and 270 is (0, 1, 0, -1, 0, H) (Pillow transposes in these cases: exact integer maps).
+ *
+ * Ops 6-9 (Brightness, Color, Contrast, Sharpness): out = blend(degenerate, image, f) per byte with a = the degenerate
+ * byte and b = the image's: t = float(a) + f * float(b - a), one fp32 product and one fp32 sum; for 0 <= f <= 1 the
+ * result is (uint8)(int)t, otherwise 0 for t <= 0, 255 for t >= 255, else (int)t.  The degenerate image: Brightness 0;
+ * Color the grey (19595 R + 38470 G + 7471 B + 32768) >> 16 in all three channels (C = 1: the input is returned);
+ * Contrast the constant floor(sum_grey / (H W) + 0.5) (C = 1: the grey is the channel itself); Sharpness Pillow's
+ * SMOOTH: interior pixels floor(acc) clipped to 0..255, acc an fp32 that starts at 0.5 and adds float(p) * k_i over
+ * the 3 x 3 window in row-major order, each step one product and one sum, k = (1, 1, 1, 1, 5, 1, 1, 1, 1) / 13 in fp32;
+ * the one-pixel border is copied.
+ *
+ * Op 10 (Posterize): out = p & (0xFF << (8 - bits)), bits = iarg (the host: (8 - (arange(31) / (30 / 6))).round()).
+ * Op 11 (Solarize): out = p if float(p) < farg else 255 - p (the host: farg = 255 * linspace(1, 0, 31)[bin]).
+ * Op 12 (AutoContrast): per channel lo / hi = the minimum / maximum; hi <= lo: unchanged; otherwise
+ *   lut[i] = clip(int(i * scale + offset), 0, 255) in fp64 with scale = 255.0 / (hi - lo), offset = -lo * scale.
+ * Op 13 (Equalize): PIL.ImageOps.equalize per channel with the histogram h: fewer than two non-empty bins: unchanged;
+ *   step = (sum(h) - last non-empty bin) div 255, step == 0: unchanged; otherwise n = step div 2 and for i = 0..255:
+ *   lut[i] = min(n div step, 255); n += h[i].
+ *
+ * One workgroup per image, ONE launch per batch on `stream`; no allocation, no memset, no workspace, no wait for the
+ * device.  B == 0 launches nothing; C outside {1, 3}, an empty image, C*H*W >= 2^30 or overlapping buffers return
+ * BASD_EINVAL before anything is launched. */
+int basd_trivial_augment(const unsigned char* src, unsigned char* dst, int B, int C, int H, int W,
+                         const BasdTaugRecord* table, int* status, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,10 @@ the HIP loss path: time of the whole step and of its parts, so that the share of
 usage: trainer_step_bench.py [--batch 256] [--steps 8] [--dtype bf16|fp32] [--optimizer adamw|schedulefree]
 [--mixup torch|fused]  (torch: the op chain of trainer.mixup_cutmix; fused: basd_amd.augment, one launch per batch)
 [--teacher resnet50|vit_b] [--attn-capture torch|fused]  (vit_b: a ViT-B/16 teacher, 12 hooked attention layers;
-fused: basd_amd.attention on each block's own qkv output, one launch per layer)"""
+fused: basd_amd.attention on each block's own qkv output, one launch per layer)
+[--uint8]  (the loader's contract of mixup="fused" + image_stats: both batches arrive as bytes and are converted and
+normalised inside the fused launches)  [--trivial-augment]  (with --uint8: the flip and TrivialAugmentWide of the augmented
+batch on the device, basd_amd.trivial_augment, one launch per batch ahead of the mixer)"""
 import argparse, os, sys, time
 from types import SimpleNamespace
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +24,13 @@ ap.add_argument("--optimizer", default="adamw", choices=["adamw", "schedulefree"
 ap.add_argument("--mixup", default="torch", choices=["torch", "fused"])
 ap.add_argument("--teacher", default="resnet50", choices=["resnet50", "vit_b"])
 ap.add_argument("--attn-capture", default="torch", choices=["torch", "fused"])
+ap.add_argument("--uint8", action="store_true")
+ap.add_argument("--trivial-augment", action="store_true")
 args = ap.parse_args()
+if args.uint8 and args.mixup != "fused":
+    ap.error("--uint8 needs --mixup fused")
+if args.trivial_augment and not args.uint8:
+    ap.error("--trivial-augment needs --uint8")
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 student = SM.StockViT().to(dev)                      # DeiT-S
@@ -35,12 +44,19 @@ torch.manual_seed(42)
 ac = torch.bfloat16 if args.dtype == "bf16" else None
 tr = T.Trainer(student, cfg, teacher, student_info=SM.probe_model(student, 224), autocast_dtype=ac,
                mixup=True if args.mixup == "torch" else "fused", optimizer=args.optimizer,
-               attn_capture=args.attn_capture)
+               attn_capture=args.attn_capture,
+               image_stats={"clean": ((0.5,) * 3, (0.25,) * 3), "augmented": ((0.5,) * 3, (0.25,) * 3)} if args.uint8 else None,
+               mix_dtype=ac if args.uint8 else None, trivial_augment=args.trivial_augment)
 g = torch.Generator().manual_seed(1)
 B = args.batch
 # images with per-image structure (a random colour cast + noise) so that the teacher features are not pure noise
 imgs = (torch.randn(B, 3, 1, 1, generator=g) * 2 + torch.randn(B, 3, 224, 224, generator=g)).to(dev)
 batch = {"clean": imgs, "augmented": imgs.flip(3), "label": torch.randint(0, 1000, (B,), generator=g).to(dev)}
+step_batch = batch
+if args.uint8:
+    # the same images as bytes (x = 255 (0.5 + 0.25 v), clamped); the parts below keep the float batch
+    as_bytes = lambda t: (t * 0.25 + 0.5).clamp_(0, 1).mul_(255).to(torch.uint8)
+    step_batch = {"clean": as_bytes(imgs), "augmented": as_bytes(imgs.flip(3)), "label": batch["label"]}
 
 
 def timed(fn, n):
@@ -53,8 +69,8 @@ def timed(fn, n):
 
 
 for _ in range(2):
-    out = tr.train_step(batch)
-step_ms = timed(lambda: tr.train_step(batch), args.steps)
+    out = tr.train_step(step_batch)
+step_ms = timed(lambda: tr.train_step(step_batch), args.steps)
 acx = torch.autocast("cuda", dtype=ac, enabled=ac is not None)
 
 
@@ -86,6 +102,6 @@ def loss_only():
 loss_only()
 l_ms = timed(loss_only, args.steps)
 print({"batch": B, "dtype": args.dtype, "optimizer": args.optimizer, "mixup": args.mixup, "teacher": args.teacher,
-       "attn_capture": args.attn_capture, "step_ms": round(step_ms, 2), "images_per_s": round(B / step_ms * 1e3, 1),
+       "attn_capture": args.attn_capture, "uint8": args.uint8, "trivial_augment": args.trivial_augment, "step_ms": round(step_ms, 2), "images_per_s": round(B / step_ms * 1e3, 1),
        "student_fwd_nograd_ms": round(s_ms, 2), "teacher_fwd_ms": round(t_ms, 2), "loss_fwd_bwd_ms": round(l_ms, 2),
        "loss_share": round(l_ms / step_ms, 3), "loss": float(out["loss"]), "ranks": dict(tr.basd_loss.layer_selector.subspace_ranks)})

@@ -13,10 +13,13 @@ Sub-modules:
   ``attention``  ``attn_importance``: a teacher's attention importance (CLS row / mean over queries) from the output of
                its own ``qkv`` projection, one launch per layer
   ``stats``    ``channel_stats`` / ``ChannelStats``: exact per-channel mean and std of uint8 images, one launch per chunk
+  ``trivial_augment``  ``TrivialAugment`` / ``draw_augment_params``: the flip and TrivialAugmentWide of uint8 batches, one
+               launch per batch
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
 __version__ = "0.1.0"
 
 from .attention import attn_importance  # noqa: E402
+from .trivial_augment import AugmentParams, TrivialAugment, draw_augment_params  # noqa: E402
 
-__all__ = ["attn_importance"]
+__all__ = ["attn_importance", "AugmentParams", "TrivialAugment", "draw_augment_params"]

@@ -92,11 +92,15 @@ class Trainer:
     (``torch.bfloat16``: what autocast would cast the images to anyway; default: fp32 for uint8, else the batch's own).
     ``attn_capture``: ``"torch"`` (the capture hooks of ``basd_amd.capture`` with torch ops) or ``"fused"`` (the teacher's
     attention importance from the output of each hooked block's own ``qkv`` Linear, one HIP launch per layer,
-    ``basd_amd.attention``; GPU only)."""
+    ``basd_amd.attention``; GPU only).
+    ``trivial_augment``: ``True`` runs the reference's ``RandomHorizontalFlip(flip_p) -> TrivialAugmentWide`` on the uint8
+    ``augmented`` batch in one HIP launch (``basd_amd.trivial_augment``; GPU only) ahead of the mixing launch, so the loader
+    only decodes and crops; it needs ``mixup="fused"`` and ``image_stats``.  The draws are made per step on the global CPU
+    generator, or taken from the batch's optional ``"augment_params"`` entry (an ``AugmentParams``)."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
-                 attn_capture: str = "torch") -> None:
+                 attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5) -> None:
         self.config = config
         self.device = next(student_model.parameters()).device
         self.criterion = nn.CrossEntropyLoss(label_smoothing=config.training.label_smoothing)
@@ -144,6 +148,14 @@ class Trainer:
                                            out_dtype=mix_dtype, device=self.device)
         elif mix_dtype is not None:
             raise ValueError("mix_dtype needs mixup='fused'")
+        self._augmenter = None
+        if trivial_augment:
+            if mixup != "fused" or image_stats is None:
+                raise ValueError("trivial_augment needs mixup='fused' and image_stats (it hands its uint8 batch to the "
+                                 f"fused launch); got mixup={mixup!r}, image_stats="
+                                 f"{'given' if image_stats is not None else None}")
+            from .trivial_augment import TrivialAugment
+            self._augmenter = TrivialAugment(device=self.device, flip_p=flip_p)
         self.best_val_acc = 0.0
         self.metrics_history = defaultdict(list)
         self._params = [p for p in student_model.parameters() if p.requires_grad]
@@ -178,6 +190,11 @@ class Trainer:
                                 f"are part of the fused launch); got mixup={self.mixup!r}, image_stats="
                                 f"{'given' if self.image_stats is not None else None}, clean {clean.dtype} "
                                 f"{tuple(clean.shape)}, augmented {student_imgs.dtype} {tuple(student_imgs.shape)}")
+        if self._augmenter is not None:
+            if student_imgs.dtype != torch.uint8:
+                raise TypeError("trivial_augment works on uint8 batches (the loader decodes and crops, nothing else); got "
+                                f"augmented {student_imgs.dtype} {tuple(student_imgs.shape)}")
+            student_imgs = self._augmenter(student_imgs, batch.get("augment_params"))
         if self.mixup == "fused":
             from .augment import MixParams
             if clean.dtype == torch.uint8:
