@@ -15,11 +15,16 @@ Sub-modules:
   ``stats``    ``channel_stats`` / ``ChannelStats``: exact per-channel mean and std of uint8 images, one launch per chunk
   ``trivial_augment``  ``TrivialAugment`` / ``draw_augment_params``: the flip and TrivialAugmentWide of uint8 batches, one
                launch per batch
+  ``resize``   ``ResizeCrop`` / ``pack_images`` / ``collate_ragged`` / ``draw_crop_params``: Pillow-exact crops and resizes
+               of ragged batches of decoded uint8 images, both views in one launch
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
 __version__ = "0.1.0"
 
 from .attention import attn_importance  # noqa: E402
 from .trivial_augment import AugmentParams, TrivialAugment, draw_augment_params  # noqa: E402
+from .resize import (CropParams, RaggedBatch, ResizeCrop, collate_ragged, draw_crop_params,  # noqa: E402
+                     eval_window, pack_images)
 
-__all__ = ["attn_importance", "AugmentParams", "TrivialAugment", "draw_augment_params"]
+__all__ = ["attn_importance", "AugmentParams", "TrivialAugment", "draw_augment_params", "CropParams", "RaggedBatch",
+           "ResizeCrop", "collate_ragged", "draw_crop_params", "eval_window", "pack_images"]

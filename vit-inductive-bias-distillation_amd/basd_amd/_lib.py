@@ -120,6 +120,7 @@ SIGNATURES = {
     "basd_attn_importance": [vp, i32, i64, i64, i32, i32, i32, i32, i32, f32, vp, vp],
     "basd_channel_stats": [vp, i32, i64, i32, i64, vp, i32, vp],
     "basd_trivial_augment": [vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "basd_resize_crop": [vp, i64, vp, i32, i32, i32, i32, vp, vp, i32, vp],
 }
 
 class ProcrustesArgs(C.Structure):

@@ -111,7 +111,7 @@ def _label_smoothing_of(criterion) -> float:
 
 @torch.no_grad()
 def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_classes: int, valid_indices=None,
-                   distributed: bool = False, image_stats=None, input_dtype=None) -> dict:
+                   distributed: bool = False, image_stats=None, input_dtype=None, resize_crop=None) -> dict:
     """The reference's ``evaluate_model``: batches are dicts with ``pixel_values`` and ``label``; returns ``val_acc``,
     ``val_acc_top5`` (percent) and ``loss`` (mean of ``criterion`` over the samples); fewer than 5 evaluated classes
     raise ``ValueError``.  ``distributed=True``: every rank iterates its own shard and the counts are summed over the
@@ -120,8 +120,14 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
     ``ToImage()``-only pipeline): they are scaled and normalised on the device by one convert-only launch of
     ``basd_amd.augment.BatchMixer`` (``MixParams("none")``) that writes ``input_dtype`` (default fp32).  A uint8 batch
     without ``image_stats`` raises ``TypeError`` before the model sees it.  Float batches go to the model as they are,
-    whatever ``image_stats`` and ``input_dtype`` say."""
+    whatever ``image_stats`` and ``input_dtype`` say.
+    ``resize_crop``: a ``basd_amd.resize.ResizeCrop``; with it a batch may carry ``images`` (a ``RaggedBatch`` of decoded
+    images, ``collate_fn=collate_ragged``) instead of ``pixel_values``: one launch makes the clean view (``Resize ->
+    CenterCrop``), which then takes the uint8 path above, so ``image_stats`` is needed (``ValueError`` otherwise)."""
     label_smoothing = _label_smoothing_of(criterion)
+    if resize_crop is not None and image_stats is None:
+        raise ValueError("resize_crop needs image_stats=(mean, std): its uint8 batches are converted and normalised on "
+                         "the device; got image_stats=None")
     model.eval()
     device = next(model.parameters()).device
     acc = EvalAccumulator(num_classes, valid_indices=valid_indices, label_smoothing=label_smoothing, top_k=5,
@@ -132,7 +138,12 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
         mean, std = image_stats
         converter = BatchMixer(num_classes, mean=mean, std=std, out_dtype=input_dtype, device=device)
     for batch in data_loader:
-        inputs = batch["pixel_values"]
+        if "images" in batch and "pixel_values" not in batch:
+            if resize_crop is None:
+                raise TypeError("a batch of decoded 'images' needs resize_crop=ResizeCrop(...); got resize_crop=None")
+            inputs = resize_crop(batch["images"].to(device, non_blocking=True), views=("clean",))["clean"]
+        else:
+            inputs = batch["pixel_values"]
         if inputs.dtype == torch.uint8 and converter is None:
             raise TypeError("uint8 pixel_values need image_stats=(mean, std): the conversion and the normalisation run "
                             f"on the device; got {inputs.dtype} of shape {tuple(inputs.shape)} and image_stats=None")

@@ -96,11 +96,18 @@ class Trainer:
     ``trivial_augment``: ``True`` runs the reference's ``RandomHorizontalFlip(flip_p) -> TrivialAugmentWide`` on the uint8
     ``augmented`` batch in one HIP launch (``basd_amd.trivial_augment``; GPU only) ahead of the mixing launch, so the loader
     only decodes and crops; it needs ``mixup="fused"`` and ``image_stats``.  The draws are made per step on the global CPU
-    generator, or taken from the batch's optional ``"augment_params"`` entry (an ``AugmentParams``)."""
+    generator, or taken from the batch's optional ``"augment_params"`` entry (an ``AugmentParams``).
+    ``resize_crop``: ``True`` makes both views on the device (``basd_amd.resize``; GPU only): the batch carries ``"images"``
+    (a ``RaggedBatch`` of decoded images: the loader only decodes, ``collate_fn=collate_ragged``) and ``"label"`` instead of
+    ``"clean"`` / ``"augmented"``, and one HIP launch resizes and crops the clean view (``Resize -> CenterCrop``) and the
+    augmented one (``RandomResizedCrop``) to ``config.model.vit.img_size`` with ``config.data.eval_crop_ratio``; it needs
+    ``mixup="fused"`` and ``image_stats``.  The crops are drawn per step on the global CPU generator, or taken from the
+    batch's optional ``"crop_params"`` entry (a ``CropParams``).  ``prepare_views(batch)`` returns the two batches."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
-                 attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5) -> None:
+                 attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
+                 resize_crop: bool = False) -> None:
         self.config = config
         self.device = next(student_model.parameters()).device
         self.criterion = nn.CrossEntropyLoss(label_smoothing=config.training.label_smoothing)
@@ -156,6 +163,14 @@ class Trainer:
                                  f"{'given' if image_stats is not None else None}")
             from .trivial_augment import TrivialAugment
             self._augmenter = TrivialAugment(device=self.device, flip_p=flip_p)
+        self._resizer = None
+        if resize_crop:
+            if mixup != "fused" or image_stats is None:
+                raise ValueError("resize_crop needs mixup='fused' and image_stats (it hands its uint8 batches to the "
+                                 f"fused launches); got mixup={mixup!r}, image_stats="
+                                 f"{'given' if image_stats is not None else None}")
+            from .resize import ResizeCrop
+            self._resizer = ResizeCrop(config.model.vit.img_size, config.data.eval_crop_ratio, device=self.device)
         self.best_val_acc = 0.0
         self.metrics_history = defaultdict(list)
         self._params = [p for p in student_model.parameters() if p.requires_grad]
@@ -178,10 +193,23 @@ class Trainer:
                 self.optimizer.zero_grad_in_step = True
 
     # -- one batch: the body of the reference's _train_epoch loop (trainer.py:133-164)
+    def prepare_views(self, batch: dict):
+        """``(clean, augmented)`` of a batch on the device.  With ``resize_crop`` both are made from the batch's
+        ``"images"`` by one launch (uint8, ``(B, C, S, S)``); without, they are the batch's own entries."""
+        dev = self.device
+        if self._resizer is None:
+            return batch["clean"].to(dev, non_blocking=True), batch["augmented"].to(dev, non_blocking=True)
+        from .resize import RaggedBatch
+        images = batch.get("images")
+        if not isinstance(images, RaggedBatch):
+            raise TypeError("resize_crop works on decoded images (the loader decodes, nothing else): the batch needs "
+                            f"'images', a RaggedBatch (collate_fn=collate_ragged); got {sorted(batch)}")
+        views = self._resizer(images.to(dev, non_blocking=True), batch.get("crop_params"))
+        return views["clean"], views["augmented"]
+
     def train_step(self, batch: dict) -> dict:
         dev = self.device
-        clean = batch["clean"].to(dev, non_blocking=True)
-        student_imgs = batch["augmented"].to(dev, non_blocking=True)
+        clean, student_imgs = self.prepare_views(batch)
         targets = batch["label"].to(dev, non_blocking=True)
         mixed_targets = targets
         if clean.dtype == torch.uint8 or student_imgs.dtype == torch.uint8:
@@ -274,14 +302,16 @@ class Trainer:
         criterion -- one HIP launch per batch, one read-back per epoch; over the ranks' shards when a process group
         with more than one rank exists.  With ``image_stats`` the validation loader may hand over uint8
         ``pixel_values``: they are normalised on the device with the ``augmented`` statistics -- the dataset's own, which
-        the reference's validation loader uses too (datasets.py:168-175) -- and written as ``mix_dtype``.  Has the
+        the reference's validation loader uses too (datasets.py:168-175) -- and written as ``mix_dtype``.  With
+        ``resize_crop`` it may hand over ``images`` (a ``RaggedBatch``) instead: they are resized and cropped first.  Has the
         signature ``train(..., evaluate=)`` expects: ``trainer.train(train_loader, val_loader,
         evaluate=trainer.evaluate)``."""
         from .evaluation import evaluate_model
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         stats = None if self.image_stats is None else self.image_stats["augmented"]
         return evaluate_model(model, val_loader, self.criterion, num_classes=self.config.model.num_classes,
-                              distributed=distributed, image_stats=stats, input_dtype=self.mix_dtype)
+                              distributed=distributed, image_stats=stats, input_dtype=self.mix_dtype,
+                              resize_crop=self._resizer)
 
     def train(self, train_loader, val_loader=None, start_epoch: int = 0, *, evaluate=None, on_epoch_end=None) -> dict:
         """The reference's epoch loop (trainer.py:171-216): ``_train_epoch``, validation, ``metrics_history``,
