@@ -106,6 +106,9 @@ int basd_syrk_multi(const void* const* x_ptrs, int dtype, long sb, long sn, long
 /* ---- one-sided Jacobi SVD / symmetric eigensolver ------------------------------------------ */
 
 int basd_jacobi_workspace_ints(int batch, int max_sweeps);
+/* Longest column (rows_dot; riding rows likewise) basd_jacobi_onesided has a kernel shape for, hence also the largest
+ * order of a plain square problem. */
+int basd_jacobi_max_rows(void);
 /* 1 when basd_jacobi_onesided takes large batches of plain n x n matrices with 4 lanes per column pair in LDS (orders
  * 40..144): basd_procrustes_forward_fused then solves the TRANSPOSED cores, without riding rows. */
 int basd_jacobi_plain4_fits(int n);
@@ -114,7 +117,10 @@ int basd_jacobi_plain4_fits(int n);
  * right rotations orthogonalise the first rows_dot rows; colnorm receives the column norms.
  * replaces the LAPACK calls behind torch.linalg.eigvalsh (layer_selector.py:16), torch.linalg.svd
  * (:36, :92), torch.linalg.svdvals (:99) and torch.linalg.matrix_norm(ord="nuc") (relational.py:48).
- * n_arr (nullable): per-matrix order for square problems.  flags: basd_jacobi_workspace_ints() ints.
+ * n_arr (nullable): per-matrix order 0 <= n_arr[m] <= n for plain square problems (no riding rows); storage stays that
+ * of the largest problem, and what lies outside a matrix's leading n_arr[m] x n_arr[m] block is left alone.  Taken at
+ * every order up to basd_jacobi_max_rows(): in LDS up to 192, by the block path beyond.
+ * flags: basd_jacobi_workspace_ints() ints.
  * tol_cos: stop when every pair has |cos| <= tol_cos over a full sweep (<= 0: eps * sqrt(rows_dot)). */
 /* Test / tuning hook: lanes per column pair of the LDS-resident solver; 0 = automatic (batches >= 256 of stacked
  * matrices: 4 lanes for n >= 40, 8 for n >= 16 -- fewer instruction issues per matrix round; else one DPP row of 16),

@@ -27,6 +27,7 @@ SIGNATURES = {
     "basd_syrk_splits": [i32, i32, i32],
     "basd_syrk_multi": [vp, i32, i64, i64, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, i32, vp, i32, i32, vp],
     "basd_jacobi_workspace_ints": [i32, i32],
+    "basd_jacobi_max_rows": [],
     "basd_jacobi_twopass_workspace_bytes": [i32, i32, i32],
     "basd_jacobi_stacked_twopass": [vp, i64, i32, i32, vp, i32, i32, f32, vp, vp, vp],
     "basd_jacobi_tuning": [i32],

@@ -838,6 +838,7 @@ class GrassmannianLayerSelector(nn.Module):
         dev = ranks_dev.device
         ranks = ranks_host if ranks_host is not None else self._read_ranks(st, keys)
         kmax = max(ranks)
+        ops.check_angle_order(kmax)
         if (not want_grad and st["tri"] and not st["stud_jacobi"] and "t_ts" in st and "s_ts" in st
                 and st["student_stream"] is None):
             # the common case: one library call queues the whole tail (host time is on the step's critical path)
@@ -981,6 +982,7 @@ class GrassmannianLayerSelector(nn.Module):
         kmax = max(int(self.subspace_ranks[t]) for t in teacher_indices)
         if kmax < 1:
             raise _rank_zero_error()
+        ops.check_angle_order(kmax)
         gram, _ = ops.centered_grams([x])                                     # :88-91 (proj_s folded below)
         ts = ops.tridiag_eigenvalues(gram)
         v_s = ops.tridiag_eigenvectors(ts, kmax)[0]                           # (kmax, d_s): Vt of the raw tokens

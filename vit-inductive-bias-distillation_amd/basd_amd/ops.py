@@ -244,13 +244,38 @@ def centered_grams(xs: list[torch.Tensor], *, centered: list[bool] | None = None
 # --------------------------------------------------------------------------- #
 # Jacobi solver
 # --------------------------------------------------------------------------- #
+def jacobi_max_order() -> int:
+    """Largest order of a square problem (longest column) the one-sided Jacobi has a kernel shape for."""
+    return _lib.query("basd_jacobi_max_rows")
+
+
+def check_angle_order(kmax: int, what: str = "principal angles") -> None:
+    """The k x k cosine matrices of the selector have the order of the largest teacher rank: say which order is too
+    large, and what the limit is, before the solver's status code does."""
+    limit = jacobi_max_order()
+    if kmax > limit:
+        raise ValueError(f"{what}: order {kmax} (the largest teacher rank) exceeds the largest order {limit} "
+                         "the one-sided Jacobi solver takes")
+
+
 def jacobi_onesided(W: torch.Tensor, rows_dot: int, *, n_arr: torch.Tensor | None = None,
                     want_sweeps: bool = False, tol: float = 0.0):
     """In-place one-sided Jacobi on W: (batch, n, rows_tot) memory == column-major (rows_tot x n).
+    ``n_arr`` (int32, device, (batch,)): per-matrix orders <= n of plain square problems (rows_dot == rows_tot == n);
+    what lies outside a matrix's leading block, column norms included, is left as it was.
     Returns column norms (batch, n) [and the sweep counts]."""
     _require_cuda(W)
     assert W.dtype == torch.float32 and W.is_contiguous() and W.dim() == 3
     batch, n, rows_tot = W.shape
+    limit = jacobi_max_order()
+    if max(rows_dot, rows_tot - rows_dot) > limit:
+        raise ValueError(f"jacobi_onesided: columns of {rows_dot} (+ {rows_tot - rows_dot} riding) rows, order {n}, "
+                         f"exceed the largest order {limit} the solver takes")
+    if n_arr is not None:
+        if not (rows_dot == rows_tot == n):
+            raise ValueError(f"jacobi_onesided: per-matrix orders need plain square storage, got {rows_tot} x {n} "
+                             f"with {rows_dot} dot rows")
+        assert n_arr.dtype == torch.int32 and n_arr.is_contiguous() and n_arr.numel() == batch
     colnorm = torch.empty((batch, n), device=W.device, dtype=torch.float32)
     flags = torch.empty((_lib.query("basd_jacobi_workspace_ints", batch, MAX_SWEEPS),), device=W.device,
                         dtype=torch.int32)

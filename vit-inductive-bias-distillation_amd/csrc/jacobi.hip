@@ -597,10 +597,14 @@ __global__ void __launch_bounds__(512) jacobi_apply_log_kernel(float* __restrict
 // columns are short: 288 rows x 112 columns at cfg-5 is 3 rounds per sweep where one wave per pair and 32 columns
 // took 9).  Columns are padded to LPP * EPL rows.  flags[m * max_sweeps + s] != 0 <=> sweep s applied a rotation above
 // sqrt(tol), i.e. another sweep follows.
+// n_arr (nullable): square problems of per-matrix order n_arr[m] <= n_max, as in jacobi_lds_kernel -- rows follow the
+// order, the storage (ld, batch_stride) and the block grid (nblk, BW) are those of the largest problem.  Block pairs
+// that lie past a matrix's own order have no column pair to rotate and return before they stage anything.
 // ---------------------------------------------------------------------------
 template <int EPL, int DOT, int LPP>
 __global__ void __launch_bounds__(1024) jacobi_block_round_kernel(float* __restrict__ W, long batch_stride,
-                                                                  int rows_dot, int rows_tot, int n, int nblk, int BW,
+                                                                  int rows_dot_max, int ld, int n_max,
+                                                                  const int* __restrict__ n_arr, int nblk, int BW,
                                                                   int round, int sweep, int max_sweeps,
                                                                   float tol, int* __restrict__ flags,
                                                                   int* __restrict__ norm2_bits) {
@@ -613,6 +617,17 @@ __global__ void __launch_bounds__(1024) jacobi_block_round_kernel(float* __restr
     int bi, bj;
     rr_pair(nblk, round, blockIdx.x, bi, bj);
     if (bi > bj) { const int t = bi; bi = bj; bj = t; }
+    // order and rows of this matrix (never past the storage, whatever n_arr holds)
+    int n = n_max, rows_dot = rows_dot_max, rows_tot = ld;
+    if (n_arr) {
+        n = n_arr[m] < n_max ? n_arr[m] : n_max;
+        rows_dot = n;
+        rows_tot = n;
+    }
+    // Nothing to rotate (uniform over the workgroup, before any barrier): block I holds no column of this matrix, or
+    // block J holds none and the pairs inside I are not this round's (they belong to round 0).  What such a workgroup
+    // would write back is what it read.
+    if (bi * BW >= n || (round > 0 && bj * BW >= n)) return;
     float* Wm = W + (long)m * batch_stride;
     const int tid = threadIdx.x;
     const int grp = tid / LPP, gl = tid % LPP;
@@ -626,7 +641,7 @@ __global__ void __launch_bounds__(1024) jacobi_block_round_kernel(float* __restr
         for (int idx = tid; idx < 2 * BW * LD; idx += NT) lds[idx] = 0.f;
         __syncthreads();
     }
-    const bool vec4 = (rows_tot & 3) == 0 && (batch_stride & 3) == 0 && (((uintptr_t)W) & 15) == 0;
+    const bool vec4 = (rows_tot & 3) == 0 && (ld & 3) == 0 && (batch_stride & 3) == 0 && (((uintptr_t)W) & 15) == 0;
     if (vec4) {
         const int q4 = rows_tot >> 2, total4 = 2 * BW * q4;
 #pragma unroll 4
@@ -634,7 +649,7 @@ __global__ void __launch_bounds__(1024) jacobi_block_round_kernel(float* __restr
             const int lc = idx / q4, r = (idx - lc * q4) << 2;
             const int gc = (lc < BW ? bi * BW + lc : bj * BW + (lc - BW));
             if (gc < n) {
-                const float4 v = *(const float4*)(Wm + (long)gc * rows_tot + r);
+                const float4 v = *(const float4*)(Wm + (long)gc * ld + r);
                 float* col = lds + lc * LD;
                 col[lds_row<EPL, DOT, LPP>(r, rows_dot)] = v.x;
                 col[lds_row<EPL, DOT, LPP>(r + 1, rows_dot)] = v.y;
@@ -647,7 +662,7 @@ __global__ void __launch_bounds__(1024) jacobi_block_round_kernel(float* __restr
         for (int idx = tid; idx < 2 * BW * rows_tot; idx += NT) {
             const int lc = idx / rows_tot, r = idx - lc * rows_tot;
             const int gc = (lc < BW ? bi * BW + lc : bj * BW + (lc - BW));
-            if (gc < n) lds[lc * LD + lds_row<EPL, DOT, LPP>(r, rows_dot)] = Wm[(long)gc * rows_tot + r];
+            if (gc < n) lds[lc * LD + lds_row<EPL, DOT, LPP>(r, rows_dot)] = Wm[(long)gc * ld + r];
         }
     }
     float* n2 = lds + 2 * BW * LD;      // cached squared column norms
@@ -703,7 +718,7 @@ __global__ void __launch_bounds__(1024) jacobi_block_round_kernel(float* __restr
                 v.z = col[lds_row<EPL, DOT, LPP>(r + 2, rows_dot)];
                 v.w = col[lds_row<EPL, DOT, LPP>(r + 3, rows_dot)];
                 v.x = fmaf(v.x, dv, v.x); v.y = fmaf(v.y, dv, v.y); v.z = fmaf(v.z, dv, v.z); v.w = fmaf(v.w, dv, v.w);
-                *(float4*)(Wm + (long)gc * rows_tot + r) = v;
+                *(float4*)(Wm + (long)gc * ld + r) = v;
             }
         }
     } else {
@@ -713,7 +728,7 @@ __global__ void __launch_bounds__(1024) jacobi_block_round_kernel(float* __restr
             const int gc = (lc < BW ? bi * BW + lc : bj * BW + (lc - BW));
             if (gc < n) {
                 const float v = lds[lc * LD + lds_row<EPL, DOT, LPP>(r, rows_dot)];
-                Wm[(long)gc * rows_tot + r] = fmaf(v, dev[lc], v);
+                Wm[(long)gc * ld + r] = fmaf(v, dev[lc], v);
             }
         }
     }
@@ -729,9 +744,14 @@ __global__ void block_sweeps_kernel(const int* __restrict__ flags, int batch, in
 }
 
 // column norms of a column-major batch (after the block solver). grid = (ceil(n/4), batch), block 256
+// n_arr (nullable): per-matrix order of square problems; columns past it are left alone, as jacobi_lds_kernel leaves them
 __global__ void colnorm_kernel(const float* __restrict__ W, long batch_stride, int rows_dot, int rows_tot, int n,
-                               float* __restrict__ colnorm, int colnorm_stride) {
+                               const int* __restrict__ n_arr, float* __restrict__ colnorm, int colnorm_stride) {
     const int m = blockIdx.y, c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (n_arr) {
+        n = n_arr[m] < n ? n_arr[m] : n;
+        rows_dot = n;
+    }
     if (c >= n) return;
     const float* col = W + (long)m * batch_stride + (long)c * rows_tot;
     float a = 0.f;
@@ -802,6 +822,11 @@ extern "C" {
 
 int basd_jacobi_workspace_ints(int batch, int max_sweeps) { return 2 * batch * max_sweeps; }
 
+// Longest column (rows_dot, and riding rows) the block path of basd_jacobi_onesided has a panel shape for: 64 lanes
+// per column pair x 16 elements per lane.  Also the largest order of a plain square problem, per-matrix orders included.
+#define BASD_JACOBI_MAX_ROWS 1024
+int basd_jacobi_max_rows(void) { return BASD_JACOBI_MAX_ROWS; }
+
 // 1 when basd_jacobi_onesided solves a batch (>= 128) of plain n x n matrices in LDS with 4 lanes per column pair
 // (orders 40..144): the transposed Procrustes cores then need no riding rows (basd_procrustes_forward_fused).
 // column stride (floats) of the plain 4-lane solver for e elements per lane: 4 e, + 8 unless that is 8 x odd already
@@ -815,8 +840,8 @@ int basd_jacobi_plain4_fits(int n) {
     return 0;
 }
 
-// 1 when basd_jacobi_onesided keeps square matrices of order n in LDS with 16 lanes per column pair: the only form that
-// takes per-matrix orders (n_arr), i.e. the principal-angle matrices of basd_selector_tail / basd_selector_chain_tail.
+// 1 when basd_jacobi_onesided keeps square matrices of order n in LDS with 16 lanes per column pair and solves them in
+// one launch: the form basd_selector_chain_tail queues speculatively for its principal-angle matrices.
 int basd_jacobi_lds_square_fits(int n) {
     if (n < 1) return 0;
     const int n_even = (n + 1) & ~1, epl = (n + 15) / 16;
@@ -845,8 +870,10 @@ int basd_jacobi_ordering(int odd_even) {
 }
 
 // One-sided Jacobi on `batch` column-major matrices (rows_tot x n, leading dim rows_tot).
-//   n_arr (device, nullable): per-matrix order for square problems (rows = n_arr[m]); the
-//   storage still uses rows_tot / batch_stride of the largest problem.
+//   n_arr (device, nullable): per-matrix order 0 <= n_arr[m] <= n for plain square problems (rows = n_arr[m]; not
+//   with riding rows); the storage still uses rows_tot / batch_stride of the largest problem, and what lies outside
+//   a matrix's leading n_arr[m] x n_arr[m] block (colnorm past n_arr[m] included) is left alone.  Taken by the
+//   16-lane LDS-resident solver (orders <= 192) and by the block path (up to BASD_JACOBI_MAX_ROWS).
 //   colnorm: (batch, colnorm_stride) column norms over the first rows_dot rows.
 //   flags: device scratch of basd_jacobi_workspace_ints() ints (block path only, may be null
 //   when the LDS path is taken).
@@ -1054,7 +1081,7 @@ int basd_jacobi_onesided(float* W, long batch_stride, int rows_dot, int rows_tot
     }
 
     // ---- block path: one launch per round-robin round over blocks of BW columns ----
-    BASD_CHECK_ARG(n_arr == nullptr && flags != nullptr);
+    BASD_CHECK_ARG(flags != nullptr);
     // Panel shape: lanes per column pair (64 / 32 / 16), elements per lane, columns per block.  A sweep is nblk - 1
     // trips of the whole matrix through L2 / HBM, so: the widest panel that fits LDS; ties go to more lanes per pair.
     struct Shape { int lpp, epl, dot, bw, nblk; };
@@ -1096,7 +1123,7 @@ int basd_jacobi_onesided(float* W, long batch_stride, int rows_dot, int rows_tot
         for (int s = 0; s < max_sweeps; ++s)                                                                     \
             for (int r = 0; r < nblk - 1; ++r)                                                                   \
                 jacobi_block_round_kernel<E, D, LP><<<dim3(nblk / 2, batch), LP * BW, panel_bytes, stream>>>(    \
-                    W, batch_stride, rows_dot, rows_tot, n, nblk, BW, r, s, max_sweeps, tol, flags,              \
+                    W, batch_stride, rows_dot, rows_tot, n, n_arr, nblk, BW, r, s, max_sweeps, tol, flags,       \
                     flags + (size_t)batch * max_sweeps);                                                         \
     } while (0)
 #define LAUNCH_BLOCK_SEL(Q, LP)                      \
@@ -1141,7 +1168,7 @@ int basd_jacobi_onesided(float* W, long batch_stride, int rows_dot, int rows_tot
 #undef LAUNCH_BLOCK
     if (!launched) return BASD_EUNSUPPORTED;
     if (sweeps_out) block_sweeps_kernel<<<(batch + 255) / 256, 256, 0, stream>>>(flags, batch, max_sweeps, sweeps_out);
-    colnorm_kernel<<<dim3((n + 3) / 4, batch), 256, 0, stream>>>(W, batch_stride, rows_dot, rows_tot, n, colnorm,
+    colnorm_kernel<<<dim3((n + 3) / 4, batch), 256, 0, stream>>>(W, batch_stride, rows_dot, rows_tot, n, n_arr, colnorm,
                                                                  colnorm_stride);
     BASD_RETURN_LAST();
 }
