@@ -17,6 +17,7 @@ Sub-modules:
                launch per batch
   ``resize``   ``ResizeCrop`` / ``pack_images`` / ``collate_ragged`` / ``draw_crop_params``: Pillow-exact crops and resizes
                of ragged batches of decoded uint8 images, both views in one launch
+  ``_launch``  what those one-launch stages share on the host: argument checks, dtype codes, the record-table uploader
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
 __version__ = "0.1.0"

@@ -11,11 +11,11 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._launch import DTYPE_CODES, raw_stream, require_gpu
 
 __all__ = ["attn_importance", "MODES"]
 
 MODES = {"cls_row": 0, "query_mean": 1}                  # BASD_ATTN_CLS_ROW / BASD_ATTN_QUERY_MEAN of include/basd_hip.h
-_DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}     # BASD_DTYPE_*
 MAX_TOKENS, MAX_HEAD_DIM = 1025, 128
 
 
@@ -37,7 +37,7 @@ def attn_importance(qkv: torch.Tensor, num_heads: int, *, mode: str, scale=None,
         raise ValueError(f"the last axis of qkv (shape {tuple(qkv.shape)}) is not 3 * num_heads * head_dim for "
                          f"num_heads = {num_heads}")
     hd = C3 // (3 * num_heads)
-    if qkv.dtype not in _DTYPE_CODES:
+    if qkv.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"qkv must be fp32 or bf16 (got {qkv.dtype}, shape {tuple(qkv.shape)})")
     if B < 1 or not 1 <= N <= MAX_TOKENS:
         raise ValueError(f"qkv of shape {tuple(qkv.shape)}: need B >= 1 and 1 <= N <= {MAX_TOKENS}")
@@ -52,12 +52,10 @@ def attn_importance(qkv: torch.Tensor, num_heads: int, *, mode: str, scale=None,
                              f"{out.dtype}, strides {out.stride()})")
         if out.device != qkv.device:
             raise ValueError(f"out lives on {out.device}, qkv on {qkv.device}")
-    if not qkv.is_cuda:
-        raise RuntimeError(f"basd_amd kernels need CUDA/HIP tensors (there is no CPU fallback); qkv of shape "
-                           f"{tuple(qkv.shape)} lives on {qkv.device}")
+    require_gpu(qkv, f"the qkv activations of shape {(B, N, C3)}")
     if out is None:
         out = torch.empty((B, num_heads, N), dtype=torch.float32, device=qkv.device)
-    _lib.call("basd_attn_importance", qkv.data_ptr(), _DTYPE_CODES[qkv.dtype], qkv.stride(0), qkv.stride(1), B, N,
+    _lib.call("basd_attn_importance", qkv.data_ptr(), DTYPE_CODES[qkv.dtype], qkv.stride(0), qkv.stride(1), B, N,
               num_heads, hd, MODES[mode], float(hd ** -0.5 if scale is None else scale), out.data_ptr(),
-              torch._C._cuda_getCurrentRawStream(qkv.device.index))
+              raw_stream(qkv.device.index))
     return out

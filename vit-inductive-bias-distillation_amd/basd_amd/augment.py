@@ -21,12 +21,12 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
+from ._launch import DTYPE_CODES, check_image_batch, check_out, lives_on, raw_stream, require_gpu
 
 __all__ = ["MixParams", "draw_mix_params", "BatchMixer"]
 
 _KINDS = {"none": 0, "mixup": 1, "cutmix": 2}
-_SRC_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2}         # BASD_DTYPE_* of include/basd_hip.h
-_DST_CODES = {torch.float32: 0, torch.bfloat16: 1}
+_OUT_DTYPES = (torch.float32, torch.bfloat16)
 _MAX_STAT_CHANNELS = 4                                                      # BASD_MIX_MAX_STAT_CHANNELS
 
 
@@ -71,15 +71,6 @@ def draw_mix_params(height: int, width: int, *, alpha: float = 1.0, p=(0.5, 0.5)
     return MixParams("cutmix", lam, (x1, y1, x2, y2), float(1.0 - (x2 - x1) * (y2 - y1) / (width * height)))
 
 
-def _dense_nchw(t: torch.Tensor) -> bool:
-    expected = 1
-    for size, stride in zip(reversed(t.shape), reversed(t.stride())):
-        if size != 1 and stride != expected:
-            return False
-        expected *= size
-    return True
-
-
 class BatchMixer:
     """``BatchMixer(num_classes, mean=None, std=None, out_dtype=None, device=...)``.
 
@@ -98,7 +89,7 @@ class BatchMixer:
             raise ValueError(f"num_classes must be positive (got {num_classes})")
         if (mean is None) != (std is None):
             raise ValueError("mean and std come together")
-        if out_dtype is not None and out_dtype not in _DST_CODES:
+        if out_dtype is not None and out_dtype not in _OUT_DTYPES:
             raise TypeError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
         self.device = torch.device(device)
         self.out_dtype = out_dtype
@@ -116,16 +107,9 @@ class BatchMixer:
 
     def __call__(self, images: torch.Tensor, labels=None, params: Optional[MixParams] = None, *, out=None):
         # every argument is checked before the device is: a CPU batch with a wrong argument reports the argument
-        if images.dim() != 4:
-            raise ValueError(f"images must be (B, C, H, W) (shape {tuple(images.shape)})")
-        if not _dense_nchw(images):
-            raise ValueError(f"images must be a dense NCHW batch, not channels-last or strided (shape "
-                             f"{tuple(images.shape)}, strides {images.stride()})")
-        if images.dtype not in _SRC_CODES:
-            raise TypeError(f"images must be fp32, bf16 or uint8 (got {images.dtype})")
-        if images.device.type != self.device.type or self.device.index not in (None, images.device.index):
+        B, C, H, W = check_image_batch(images, DTYPE_CODES)
+        if not lives_on(self.device, images.device):
             raise ValueError(f"images live on {images.device}, the mixer on {self.device}")
-        B, C, H, W = images.shape
         use_stats = images.dtype == torch.uint8 and self.mean is not None
         if use_stats and len(self.mean) != C:
             raise ValueError(f"{len(self.mean)} channel statistics for images of shape {tuple(images.shape)}")
@@ -150,30 +134,16 @@ class BatchMixer:
             if not (0 <= x1 <= x2 <= W and 0 <= y1 <= y2 <= H):
                 raise ValueError(f"box (x1, y1, x2, y2) = {params.box} does not lie inside a {H} x {W} image")
         if out is not None:
-            if out.shape != images.shape or not _dense_nchw(out):
-                raise ValueError(f"out must be a dense NCHW tensor of shape {tuple(images.shape)} (shape "
-                                 f"{tuple(out.shape)}, strides {out.stride()})")
-            if out.dtype not in _DST_CODES:
-                raise TypeError(f"out must be fp32 or bf16 (got {out.dtype})")
-            if out.device != images.device:
-                raise ValueError(f"out lives on {out.device}, images on {images.device}")
-            s0, d0 = images.data_ptr(), out.data_ptr()
-            s1, d1 = s0 + images.numel() * images.element_size(), d0 + out.numel() * out.element_size()
-            if s0 < d1 and d0 < s1:
-                raise ValueError(f"out overlaps images (shape {tuple(images.shape)}): row i needs the original row "
-                                 "i - 1")
-        if not images.is_cuda:
-            raise RuntimeError(f"basd_amd kernels need CUDA/HIP tensors (there is no CPU fallback); images of shape "
-                               f"{tuple(images.shape)} live on {images.device}")
+            check_out(out, images, _OUT_DTYPES, "row i needs the original row i - 1")
+        require_gpu(images, f"images of shape {(B, C, H, W)}")
         if out is None:
             out = torch.empty((B, C, H, W), dtype=out_dtype, device=images.device)
         targets = None
         if labels is not None:
             targets = torch.empty((B, self.num_classes), dtype=torch.float32, device=images.device)
-        _lib.call("basd_mix_batch", images.data_ptr(), _SRC_CODES[images.dtype], out.data_ptr(), _DST_CODES[out.dtype],
+        _lib.call("basd_mix_batch", images.data_ptr(), DTYPE_CODES[images.dtype], out.data_ptr(), DTYPE_CODES[out.dtype],
                   B, C, H, W, _KINDS[params.kind], float(params.lam), y1, y2, x1, x2,
                   self._mean_c if use_stats else None, self._std_c if use_stats else None,
                   None if labels is None else labels.data_ptr(), self.num_classes, float(params.lam_targets),
-                  None if targets is None else targets.data_ptr(),
-                  torch._C._cuda_getCurrentRawStream(images.device.index))
+                  None if targets is None else targets.data_ptr(), raw_stream(images.device.index))
         return out, targets

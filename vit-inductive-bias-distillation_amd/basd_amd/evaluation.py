@@ -19,11 +19,11 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib
+from ._launch import DTYPE_CODES, raw_stream, require_gpu
 
 __all__ = ["EvalAccumulator", "evaluate_model"]
 
 _LOSS_UNIT = 2.0 ** -32
-_DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}            # BASD_DTYPE_* of include/basd_hip.h
 
 
 class EvalAccumulator:
@@ -61,8 +61,8 @@ class EvalAccumulator:
         self.state.zero_()
 
     def update(self, logits: torch.Tensor, targets: torch.Tensor) -> None:
-        if not (logits.is_cuda and targets.is_cuda and self.state.is_cuda):
-            raise RuntimeError("basd_amd kernels need CUDA/HIP tensors (there is no CPU fallback)")
+        for t in (logits, targets, self.state):
+            require_gpu(t)
         if logits.dim() != 2 or logits.stride(1) != 1:
             raise ValueError(f"logits must be (B, C) with unit column stride (shape {tuple(logits.shape)}, strides "
                              f"{logits.stride()})")
@@ -72,7 +72,7 @@ class EvalAccumulator:
                 raise ValueError(f"{C} logit columns for num_classes = {self.num_classes}")
         elif self._max_index >= C:
             raise ValueError(f"valid_indices reach column {self._max_index} of {C}")
-        if logits.dtype not in _DTYPE_CODES:
+        if logits.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"logits must be fp32 or bf16 (got {logits.dtype})")
         if targets.dtype != torch.int64:
             raise TypeError(f"targets must be int64 class positions (got {targets.dtype})")
@@ -80,10 +80,9 @@ class EvalAccumulator:
             raise ValueError(f"targets must be a dense ({B},) tensor (shape {tuple(targets.shape)})")
         if logits.device != self.state.device or targets.device != self.state.device:
             raise ValueError("logits, targets and the accumulator must live on one device")
-        _lib.call("basd_eval_batch", logits.data_ptr(), _DTYPE_CODES[logits.dtype], logits.stride(0), B, C,
+        _lib.call("basd_eval_batch", logits.data_ptr(), DTYPE_CODES[logits.dtype], logits.stride(0), B, C,
                   None if self._index is None else self._index.data_ptr(), self.K, targets.data_ptr(),
-                  self.label_smoothing, self.top_k, self.state.data_ptr(),
-                  torch._C._cuda_getCurrentRawStream(self.state.device.index))
+                  self.label_smoothing, self.top_k, self.state.data_ptr(), raw_stream(self.state.device.index))
 
     def all_reduce(self, group=None) -> None:
         """Sum the five words over the ranks of ``group`` (every rank evaluated its own shard: ``shard_loader``)."""

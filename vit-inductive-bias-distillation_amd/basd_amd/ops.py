@@ -12,10 +12,11 @@ from functools import lru_cache
 import torch
 
 from . import _lib
+from ._launch import DTYPE_CODES, raw_stream as _stream, require_gpu
 
 import os
 
-F32, BF16 = 0, 1
+_FLOATS = (torch.float32, torch.bfloat16)       # consumed in place; DTYPE_CODES has the kernels' codes
 MAX_SWEEPS = 20
 TWO_PASS_SVD = True      # test hook: False sends cores of 129..196 tokens through the block solver instead
 TRANSPOSED_MIX_GRAD = True   # test hook: False keeps the stacked cores (riding rows) whenever the mixing weights need a gradient;
@@ -30,31 +31,23 @@ if os.environ.get("BASD_JACOBI_ORDERING") in ("0", "1"):      # A/B hook: 0 = ro
     _lib.call("basd_jacobi_ordering", int(os.environ["BASD_JACOBI_ORDERING"]))
 
 
-def _stream() -> int:
-    # the raw hipStream_t of the current stream: torch.cuda.current_stream() builds a Stream object through three layers of
-    # Python (~10 us, ~20 calls a step); this is one C call
-    return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
-
-
 def _dtype_code(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
-        return F32
-    if t.dtype == torch.bfloat16:
-        return BF16
+    if t.dtype in _FLOATS:
+        return DTYPE_CODES[t.dtype]
     raise TypeError(f"unsupported dtype {t.dtype}")
 
 
 def as_supported(t: torch.Tensor) -> torch.Tensor:
     """fp32 and bf16 are consumed in place; anything else is widened to fp32."""
-    if t.dtype in (torch.float32, torch.bfloat16):
+    if t.dtype in _FLOATS:
         return t
     return t.float()
 
 
 def _require_cuda(*tensors: torch.Tensor) -> None:
     for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("basd_amd kernels need CUDA/HIP tensors (there is no CPU fallback)")
+        if not t.is_cuda:          # the loss path comes through here: no call unless it raises
+            require_gpu(t)
 
 
 def _ptr(t: torch.Tensor | None) -> int | None:

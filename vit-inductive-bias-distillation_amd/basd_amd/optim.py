@@ -24,6 +24,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._launch import raw_stream as _stream, require_gpu
 
 __all__ = ["AdamWScheduleFree", "schedule", "MAX_GROUPS"]
 
@@ -152,8 +153,7 @@ class AdamWScheduleFree(torch.optim.Optimizer):
         table when something moved.  The chunk list depends on the sizes only and is written once per layout."""
         self._ensure_state()
         params = self._params
-        if not params[0].is_cuda:
-            raise RuntimeError("basd_amd kernels need CUDA/HIP tensors (there is no CPU fallback)")
+        require_gpu(params[0])
         signature = tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in params)
         if signature == self._signature:
             return
@@ -181,10 +181,6 @@ class AdamWScheduleFree(torch.optim.Optimizer):
         self._signature = signature
         self.table_uploads += 1
 
-    @staticmethod
-    def _stream() -> int:
-        return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
-
     # ---- the public interface ----------------------------------------------------------------------------------
     def step(self, closure=None, *, grad_scale: float | None = None, zero_grad_in_step: bool | None = None):
         """One update of every parameter that has a gradient (a parameter whose ``.grad`` is ``None`` is skipped; its
@@ -207,7 +203,7 @@ class AdamWScheduleFree(torch.optim.Optimizer):
         _lib.call("basd_sfadamw_step", self._table.data_ptr(), self._chunks.data_ptr(), self._n_chunks,
                   C.addressof(scalars), len(self.param_groups),
                   self.grad_scale if grad_scale is None else float(grad_scale),
-                  int(self.zero_grad_in_step if zero_grad_in_step is None else zero_grad_in_step), self._stream())
+                  int(self.zero_grad_in_step if zero_grad_in_step is None else zero_grad_in_step), _stream())
         return loss
 
     def _swap(self, to_train: bool) -> None:
@@ -219,7 +215,7 @@ class AdamWScheduleFree(torch.optim.Optimizer):
             beta1 = [g["betas"][0] for g in self.param_groups]
             weights = (C.c_float * len(beta1))(*[1.0 - b if to_train else 1.0 - 1.0 / b for b in beta1])
             _lib.call("basd_sfadamw_swap", self._table.data_ptr(), self._chunks.data_ptr(), self._n_chunks,
-                      C.addressof(weights), len(beta1), self._stream())
+                      C.addressof(weights), len(beta1), _stream())
         for group in self.param_groups:
             group["train_mode"] = to_train
 

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._launch import RecordTable, batch_columns, lives_on, raw_stream, require_gpu
 
 __all__ = ["RaggedBatch", "pack_images", "collate_ragged", "eval_window", "CropParams", "draw_crop_params",
            "make_records", "RECORD_DTYPE", "ResizeCrop", "resize_reference", "VIEWS", "MAX_RATIO", "MAX_SIDE"]
@@ -305,13 +306,7 @@ def make_records(sizes, image_size: int, crop_ratio: float, crop_params: Optiona
         else:
             if crop_params is None:
                 raise ValueError("the augmented view needs crop_params")
-            cols = []
-            for name in CropParams._fields:
-                t = torch.as_tensor(getattr(crop_params, name)).to(torch.int64).reshape(-1)
-                if t.numel() != B:
-                    raise ValueError(f"CropParams.{name} has {t.numel()} entries for a batch of {B}")
-                cols.append(t.tolist())
-            top, left, hh, ww = cols
+            top, left, hh, ww = batch_columns(crop_params, B, dict.fromkeys(CropParams._fields, torch.int64)).values()
             for b in range(B):
                 if not (0 <= top[b] and 0 <= left[b] and 1 <= hh[b] and 1 <= ww[b] and top[b] + hh[b] <= H[b]
                         and left[b] + ww[b] <= W[b]):
@@ -339,8 +334,6 @@ class ResizeCrop:
     largest batch seen); then exactly one launch on the current stream, no wait for the device.  ``status()`` reads
     the kernel's status word back (0: clean; it waits for the device)."""
 
-    _RING = 4
-
     def __init__(self, image_size: int, crop_ratio: float, *, device) -> None:
         self.image_size = int(image_size)
         self.crop_ratio = float(crop_ratio)
@@ -349,33 +342,17 @@ class ResizeCrop:
         if not self.crop_ratio > 0.0:
             raise ValueError(f"crop_ratio must be positive (got {crop_ratio})")
         self.device = torch.device(device)
-        self._host = []          # ring of (pinned buffer, event recorded behind its last copy)
-        self._slot = 0
-        self._table = None
-        self._status = None
-
-    def _buffers(self, records: int, device: torch.device):
-        nbytes = max(records, 1) * RECORD_DTYPE.itemsize
-        if self._table is None or self._table.numel() < nbytes:
-            self._table = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            self._host = [[torch.empty(nbytes, dtype=torch.uint8).pin_memory(), None] for _ in range(self._RING)]
-        if self._status is None:
-            self._status = torch.zeros(1, dtype=torch.int32, device=device)
-        self._slot = (self._slot + 1) % self._RING
-        slot = self._host[self._slot]
-        if slot[1] is not None and not slot[1].query():
-            slot[1].synchronize()          # the copy made from this buffer RING calls ago: done long since
-        return slot
+        self._records = RecordTable(RECORD_DTYPE)
 
     def status(self) -> int:
-        return 0 if self._status is None else int(self._status.item())
+        return self._records.status()
 
     def __call__(self, ragged: RaggedBatch, crop_params: Optional[CropParams] = None, *, views=VIEWS) -> dict:
         # every argument is checked before the device is: a CPU batch with a wrong argument reports the argument
         if not isinstance(ragged, RaggedBatch):
             raise TypeError(f"ragged must be a RaggedBatch (got {type(ragged).__name__}); pack_images makes one")
         views = _check_views(views)
-        if ragged.device.type != self.device.type or self.device.index not in (None, ragged.device.index):
+        if not lives_on(self.device, ragged.device):
             raise ValueError(f"the images live on {ragged.device}, the resizer on {self.device}")
         B, C, S = len(ragged), ragged.channels, self.image_size
         if C * S * S >= 1 << 30:
@@ -384,24 +361,15 @@ class ResizeCrop:
             crop_params = draw_crop_params(ragged.sizes)
         offsets = ragged.offsets
         checked = make_records(ragged.sizes, S, self.crop_ratio, crop_params, views=views, offsets=offsets)
-        if not ragged.data.is_cuda:
-            raise RuntimeError(f"basd_amd kernels need CUDA/HIP tensors (there is no CPU fallback); the {B} images "
-                               f"live on {ragged.device}")
+        require_gpu(ragged.data, f"the {B} images")
         n = len(views) * B
         out = torch.empty((n, C, S, S), dtype=torch.uint8, device=ragged.device)
         result = {view: out[v * B:(v + 1) * B] for v, view in enumerate(views)}
         if n == 0:
             return result
-        slot = self._buffers(n, ragged.device)
-        nbytes = n * RECORD_DTYPE.itemsize
-        slot[0].numpy()[:nbytes].view(RECORD_DTYPE)[...] = checked
-        self._table[:nbytes].copy_(slot[0][:nbytes], non_blocking=True)
-        if slot[1] is None:
-            slot[1] = torch.cuda.Event()
-        slot[1].record()
+        self._records.stage(n, ragged.device)[...] = checked
         _lib.call("basd_resize_crop", ragged.data.data_ptr(), ragged.data.numel(), out.data_ptr(), n, C, S, S,
-                  self._table.data_ptr(), self._status.data_ptr(), 0,
-                  torch._C._cuda_getCurrentRawStream(ragged.device.index))
+                  self._records.upload(), self._records.status_ptr, 0, raw_stream(ragged.device.index))
         return result
 
 

@@ -20,6 +20,7 @@ from typing import Iterable, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._launch import lives_on, raw_stream, require_gpu
 
 __all__ = ["ChannelStats", "channel_stats", "finish"]
 
@@ -88,13 +89,11 @@ class ChannelStats:
         if not images.is_contiguous():
             raise ValueError(f"images must be dense in the order of their axes (shape {shape}, strides "
                              f"{images.stride()})")
-        if not images.is_cuda:
-            raise RuntimeError(f"basd_amd kernels need CUDA/HIP tensors (there is no CPU fallback); images of shape "
-                               f"{shape} live on {images.device}")
-        if images.device.type != self.device.type or self.device.index not in (None, images.device.index):
+        require_gpu(images, f"images of shape {shape}")
+        if not lives_on(self.device, images.device):
             raise ValueError(f"images live on {images.device}, the statistics on {self.device}")
         _lib.call("basd_channel_stats", images.data_ptr(), _LAYOUTS[layout], count, C, pixels, self.state.data_ptr(),
-                  0, torch._C._cuda_getCurrentRawStream(images.device.index))
+                  0, raw_stream(images.device.index))
 
     def stream(self, images: Iterable, *, chunk_bytes: int = 64 << 20) -> None:
         """Add an iterable of PIL images, HWC uint8 numpy arrays or HWC uint8 CPU tensors of any sizes.  PIL images go
@@ -107,8 +106,7 @@ class ChannelStats:
         chunk = int(chunk_bytes) - int(chunk_bytes) % channels
         if chunk < channels:
             raise ValueError(f"chunk_bytes = {chunk_bytes} does not hold one pixel of {channels} channels")
-        if self.device.type != "cuda":
-            raise RuntimeError(f"basd_amd kernels need a CUDA/HIP device (there is no CPU fallback); got {self.device}")
+        require_gpu(self.device, "the statistics")
         staging = [torch.empty(chunk, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         free = [None, None]                                               # event: the buffer's copy has left it
         on_device = torch.empty(chunk, dtype=torch.uint8, device=self.device)

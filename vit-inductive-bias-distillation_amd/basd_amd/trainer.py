@@ -157,18 +157,12 @@ class Trainer:
             raise ValueError("mix_dtype needs mixup='fused'")
         self._augmenter = None
         if trivial_augment:
-            if mixup != "fused" or image_stats is None:
-                raise ValueError("trivial_augment needs mixup='fused' and image_stats (it hands its uint8 batch to the "
-                                 f"fused launch); got mixup={mixup!r}, image_stats="
-                                 f"{'given' if image_stats is not None else None}")
+            self._require_fused("trivial_augment needs", "it hands its uint8 batch to the fused launch")
             from .trivial_augment import TrivialAugment
             self._augmenter = TrivialAugment(device=self.device, flip_p=flip_p)
         self._resizer = None
         if resize_crop:
-            if mixup != "fused" or image_stats is None:
-                raise ValueError("resize_crop needs mixup='fused' and image_stats (it hands its uint8 batches to the "
-                                 f"fused launches); got mixup={mixup!r}, image_stats="
-                                 f"{'given' if image_stats is not None else None}")
+            self._require_fused("resize_crop needs", "it hands its uint8 batches to the fused launches")
             from .resize import ResizeCrop
             self._resizer = ResizeCrop(config.model.vit.img_size, config.data.eval_crop_ratio, device=self.device)
         self.best_val_acc = 0.0
@@ -192,6 +186,13 @@ class Trainer:
                 # the gradients stay where they are: the update zeroes them in its own pass (no separate zero_grad)
                 self.optimizer.zero_grad_in_step = True
 
+    def _require_fused(self, what: str, why: str, error=ValueError, **batches) -> None:
+        """Whatever hands uint8 batches on needs the fused launch (``mixup="fused"``) and ``image_stats`` to convert them."""
+        if self.mixup != "fused" or self.image_stats is None:
+            got = "".join(f", {name} {t.dtype} {tuple(t.shape)}" for name, t in batches.items())
+            raise error(f"{what} mixup='fused' and image_stats ({why}); got mixup={self.mixup!r}, image_stats="
+                        f"{'given' if self.image_stats is not None else None}{got}")
+
     # -- one batch: the body of the reference's _train_epoch loop (trainer.py:133-164)
     def prepare_views(self, batch: dict):
         """``(clean, augmented)`` of a batch on the device.  With ``resize_crop`` both are made from the batch's
@@ -213,11 +214,8 @@ class Trainer:
         targets = batch["label"].to(dev, non_blocking=True)
         mixed_targets = targets
         if clean.dtype == torch.uint8 or student_imgs.dtype == torch.uint8:
-            if self.mixup != "fused" or self.image_stats is None:
-                raise TypeError("uint8 batches need mixup='fused' and image_stats (the conversion and the normalisation "
-                                f"are part of the fused launch); got mixup={self.mixup!r}, image_stats="
-                                f"{'given' if self.image_stats is not None else None}, clean {clean.dtype} "
-                                f"{tuple(clean.shape)}, augmented {student_imgs.dtype} {tuple(student_imgs.shape)}")
+            self._require_fused("uint8 batches need", "the conversion and the normalisation are part of the fused launch",
+                                TypeError, clean=clean, augmented=student_imgs)
         if self._augmenter is not None:
             if student_imgs.dtype != torch.uint8:
                 raise TypeError("trivial_augment works on uint8 batches (the loader decodes and crops, nothing else); got "

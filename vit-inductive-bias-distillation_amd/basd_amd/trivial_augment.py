@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .augment import _dense_nchw
+from ._launch import RecordTable, batch_columns, check_image_batch, check_out, lives_on, raw_stream, require_gpu
 
 __all__ = ["OPS", "AugmentParams", "draw_augment_params", "posterize_bits", "magnitude", "make_records", "RECORD_DTYPE",
            "TrivialAugment"]
@@ -146,25 +146,21 @@ def affine_matrix(op: int, m: float, height: int, width: int) -> tuple:
 
 
 def _check_params(params: AugmentParams, batch: int):
-    op = torch.as_tensor(params.op).to(torch.int64).reshape(-1)
-    bin_ = torch.as_tensor(params.bin).to(torch.int64).reshape(-1)
-    sign = torch.as_tensor(params.sign).to(torch.bool).reshape(-1)
-    flip = torch.as_tensor(params.flip).to(torch.bool).reshape(-1)
-    for name, t in (("op", op), ("bin", bin_), ("sign", sign), ("flip", flip)):
-        if t.numel() != batch:
-            raise ValueError(f"AugmentParams.{name} has {t.numel()} entries for a batch of {batch}")
-    if batch and (int(op.min()) < 0 or int(op.max()) >= len(OPS)):
-        raise ValueError(f"AugmentParams.op must lie in [0, {len(OPS)}) (got {int(op.min())}..{int(op.max())})")
-    if batch and (int(bin_.min()) < 0 or int(bin_.max()) >= NUM_BINS):
-        raise ValueError(f"AugmentParams.bin must lie in [0, {NUM_BINS}) (got {int(bin_.min())}..{int(bin_.max())})")
-    return op.tolist(), bin_.tolist(), sign.tolist(), flip.tolist()
+    cols = batch_columns(params, batch, {"op": torch.int64, "bin": torch.int64, "sign": torch.bool, "flip": torch.bool})
+    for name, limit in (("op", len(OPS)), ("bin", NUM_BINS)):
+        if batch and (min(cols[name]) < 0 or max(cols[name]) >= limit):
+            raise ValueError(f"AugmentParams.{name} must lie in [0, {limit}) (got {min(cols[name])}..{max(cols[name])})")
+    return cols["op"], cols["bin"], cols["sign"], cols["flip"]
 
 
 def make_records(params: AugmentParams, height: int, width: int, out: Optional[np.ndarray] = None) -> np.ndarray:
     """The record table of ``params`` for images of ``height`` x ``width``: a ``RECORD_DTYPE`` array of B entries
     (written into ``out`` if given).  Matrices come from ``math`` in double, magnitudes from ``magnitude``."""
-    batch = int(torch.as_tensor(params.op).numel())
-    ops, bins, signs, flips = _check_params(params, batch)
+    return _records_of(*_check_params(params, int(torch.as_tensor(params.op).numel())), height, width, out)
+
+
+def _records_of(ops: list, bins: list, signs: list, flips: list, height: int, width: int, out) -> np.ndarray:
+    batch = len(ops)
     rec = np.zeros(batch, dtype=RECORD_DTYPE) if out is None else out
     if rec.shape != (batch,) or rec.dtype != RECORD_DTYPE:
         raise ValueError(f"out must hold {batch} records")
@@ -193,78 +189,32 @@ class TrivialAugment:
     batch seen); then exactly one launch on the current stream, no wait for the device.  ``status()`` reads the
     kernel's status word back (0: clean; it waits for the device)."""
 
-    _RING = 4
-
     def __init__(self, *, device, flip_p: float = 0.5) -> None:
         self.device = torch.device(device)
         self.flip_p = float(flip_p)
         if not 0.0 <= self.flip_p <= 1.0:
             raise ValueError(f"flip_p must lie in [0, 1] (got {flip_p})")
-        self._host = []          # ring of (pinned buffer, event recorded behind its last copy)
-        self._slot = 0
-        self._table = None
-        self._status = None
-
-    def _buffers(self, batch: int, device: torch.device):
-        nbytes = max(batch, 1) * RECORD_DTYPE.itemsize
-        if self._table is None or self._table.numel() < nbytes:
-            self._table = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            self._host = [[torch.empty(nbytes, dtype=torch.uint8).pin_memory(), None] for _ in range(self._RING)]
-        if self._status is None:
-            self._status = torch.zeros(1, dtype=torch.int32, device=device)
-        self._slot = (self._slot + 1) % self._RING
-        slot = self._host[self._slot]
-        if slot[1] is not None and not slot[1].query():
-            slot[1].synchronize()          # the copy made from this buffer RING calls ago: done long since
-        return slot
+        self._records = RecordTable(RECORD_DTYPE)
 
     def status(self) -> int:
-        return 0 if self._status is None else int(self._status.item())
+        return self._records.status()
 
     def __call__(self, images: torch.Tensor, params: Optional[AugmentParams] = None, *, out=None) -> torch.Tensor:
         # every argument is checked before the device is: a CPU batch with a wrong argument reports the argument
-        if images.dim() != 4:
-            raise ValueError(f"images must be (B, C, H, W) (shape {tuple(images.shape)})")
-        if not _dense_nchw(images):
-            raise ValueError(f"images must be a dense NCHW batch, not channels-last or strided (shape "
-                             f"{tuple(images.shape)}, strides {images.stride()})")
-        if images.dtype != torch.uint8:
-            raise TypeError(f"images must be uint8 (got {images.dtype}, shape {tuple(images.shape)})")
-        B, C, H, W = images.shape
-        if C not in (1, 3):
-            raise ValueError(f"images must have 1 or 3 channels (shape {tuple(images.shape)})")
-        if images.device.type != self.device.type or self.device.index not in (None, images.device.index):
+        B, C, H, W = check_image_batch(images, (torch.uint8,), channels=(1, 3))
+        if not lives_on(self.device, images.device):
             raise ValueError(f"images live on {images.device}, the augmenter on {self.device}")
         if out is not None:
-            if out.shape != images.shape or not _dense_nchw(out):
-                raise ValueError(f"out must be a dense NCHW tensor of shape {tuple(images.shape)} (shape "
-                                 f"{tuple(out.shape)}, strides {out.stride()})")
-            if out.dtype != torch.uint8:
-                raise TypeError(f"out must be uint8 (got {out.dtype})")
-            if out.device != images.device:
-                raise ValueError(f"out lives on {out.device}, images on {images.device}")
-            s0, d0 = images.data_ptr(), out.data_ptr()
-            s1, d1 = s0 + images.numel(), d0 + out.numel()
-            if s0 < d1 and d0 < s1:
-                raise ValueError(f"out overlaps images (shape {tuple(images.shape)}): an output pixel reads source "
-                                 "pixels anywhere in its image")
+            check_out(out, images, (torch.uint8,), "an output pixel reads source pixels anywhere in its image")
         if params is None:
             params = draw_augment_params(B, flip_p=self.flip_p)
-        _check_params(params, B)
-        if not images.is_cuda:
-            raise RuntimeError(f"basd_amd kernels need CUDA/HIP tensors (there is no CPU fallback); images of shape "
-                               f"{tuple(images.shape)} live on {images.device}")
+        columns = _check_params(params, B)
+        require_gpu(images, f"images of shape {(B, C, H, W)}")
         if out is None:
             out = torch.empty_like(images)
         if B == 0 or images.numel() == 0:
             return out
-        slot = self._buffers(B, images.device)
-        nbytes = B * RECORD_DTYPE.itemsize
-        make_records(params, H, W, out=slot[0].numpy()[:nbytes].view(RECORD_DTYPE))
-        self._table[:nbytes].copy_(slot[0][:nbytes], non_blocking=True)
-        if slot[1] is None:
-            slot[1] = torch.cuda.Event()
-        slot[1].record()
-        _lib.call("basd_trivial_augment", images.data_ptr(), out.data_ptr(), B, C, H, W, self._table.data_ptr(),
-                  self._status.data_ptr(), torch._C._cuda_getCurrentRawStream(images.device.index))
+        _records_of(*columns, H, W, self._records.stage(B, images.device))
+        _lib.call("basd_trivial_augment", images.data_ptr(), out.data_ptr(), B, C, H, W, self._records.upload(),
+                  self._records.status_ptr, raw_stream(images.device.index))
         return out
