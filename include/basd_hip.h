@@ -909,6 +909,118 @@ typedef struct BasdResizeRecord {
 int basd_resize_crop(const unsigned char* src, long src_bytes, unsigned char* dst, int n, int C, int OH, int OW,
                      const BasdResizeRecord* table, int* status, int band_rows, hipStream_t stream);
 
+/* ---- Pillow-exact baseline JPEG decoding of a batch of streams in three launches --------------------------- */
+
+/* Width and height of a stream the device decodes are at most this (larger ones go through the host fallback). */
+#define BASD_JPEG_MAX_SIDE 16384
+/* Images of one call (the image is the second grid axis of two of the launches). */
+#define BASD_JPEG_MAX_BATCH 65535
+
+#define BASD_JPEG_KIND_STREAM 0      /* a baseline JPEG stream, decoded on the device */
+#define BASD_JPEG_KIND_RAW 1         /* width * height * 3 RGB bytes made by the host fallback, copied into place */
+
+/* The per-image status word (0: decoded); the batch's status word is the OR of 1 << (code - 1). */
+#define BASD_JPEG_BAD_RECORD 1       /* a field of the record outside its bounds (nothing of the image is read) */
+#define BASD_JPEG_BAD_TABLE 2        /* a Huffman table that is not a prefix code, or reaches past the stream */
+#define BASD_JPEG_TRUNCATED 3        /* the entropy-coded data of a segment ends before its last coefficient */
+#define BASD_JPEG_BAD_CODE 4         /* a bit pattern that is no code of the table */
+#define BASD_JPEG_BAD_RESTART 5      /* a missing or wrong RSTn marker, or a segment count that is not the frame's */
+#define BASD_JPEG_BAD_INDEX 6        /* a coefficient index past 63 */
+#define BASD_JPEG_BAD_VALUE 7        /* a DC value outside 16 bits */
+
+/* One row of the device table, one per image (128 bytes).  Offsets into the stream are counted from src_offset. */
+typedef struct BasdJpegRecord {
+    long long src_offset;         /* byte offset of the stream (or of the raw pixels) in the byte buffer */
+    long long out_offset;         /* byte offset of the image (HWC RGB, width * height * 3 bytes) in the output */
+    long long coef_offset;        /* workspace: blocks (scan order) of 64 int16 in zigzag order (a multiple of 16) */
+    long long plane_offset;       /* workspace: the component planes, blocks * 64 bytes (a multiple of 8) */
+    long long seg_offset;         /* byte buffer: n_seg int32, the first entropy-coded byte of every segment */
+    int src_len;                  /* bytes of the stream (< 2^31 - 16); of a raw record width * height * 3 */
+    int kind;                     /* BASD_JPEG_KIND_* */
+    int width, height;
+    int ncomp;                    /* 1 or 3 */
+    int hs, vs;                   /* sampling of component 0: (1,1), (2,1) or (2,2); the others are (1,1) */
+    int restart;                  /* MCUs per restart interval (DRI), 0: none */
+    int n_seg;                    /* entropy-coded segments: 1, or ceil(MCUs / restart) */
+    int quant[3];                 /* per component: offset of the 64 bytes of its DQT table (zigzag order) */
+    int dc[3], ac[3];             /* per component: offset of its DHT table (16 counts, then the values) */
+    int pad[4];
+} BasdJpegRecord;
+
+/* Bytes at the start of the workspace that hold the B per-image status words. */
+long basd_jpeg_status_bytes(int B);
+
+/* replaces: the `Image.open(...).convert("RGB")` of the reference loader's workers (src/data/datasets.py), the last
+ *           per-image work of the host.
+ * src: one uint8 buffer of src_bytes bytes (a multiple of 16, at a 16-byte aligned address) that holds the streams, the
+ * raw pixels of the fallback's images and the int32 segment tables; out: out_bytes bytes, the images back to back as
+ * interleaved HWC RGB (the layout of a RaggedBatch of 3 channels); table: B records on the device; ws: a workspace of
+ * ws_bytes bytes (16-byte aligned) whose first basd_jpeg_status_bytes(B) bytes receive the per-image status words;
+ * status: one int on the device, OR-ed into; max_blocks / max_pixels: the largest block and pixel count of an image
+ * of the batch (they size the grids; an image with more is cut short, never written out of bounds).
+ *
+ * This text is the specification; basd_amd.jpeg.decode_reference restates it in numpy, the kernels equal it byte for
+ * byte, and it equals Pillow 12 (libjpeg-turbo) `np.asarray(Image.open(f).convert("RGB"))` byte for byte on the
+ * streams in scope: SOF0, 8 bits, 1 or 3 components, luma sampling (1,1), (2,1) or (2,2) with chroma (1,1) (one
+ * component: any sampling, read as (1,1)), 8-bit quantisation tables, one interleaved scan, no Adobe APP14 segment,
+ * three components only as YCbCr (a JFIF APP0 segment or the component ids 1, 2, 3), sides up to BASD_JPEG_MAX_SIDE.
+ * The host parses the header (basd_amd.jpeg.parse_jpeg) and names the tables by their offsets; EXIF is ignored.
+ *
+ * Geometry.  hmax = hs, vmax = vs.  An MCU is hs * vs luma blocks (row-major) followed by one Cb and one Cr block and
+ * covers 8 hs x 8 vs pixels; one component: one block, 8 x 8 pixels.  MCUs run row-major over ceil(W / (8 hs)) x
+ * ceil(H / (8 vs)).  Component planes have ceil(W h / hmax) x ceil(H v / vmax) real samples (the rest of the blocks'
+ * area is decoded and never shown).
+ *
+ * Entropy decode.  A Huffman table assigns canonical codes: code = 0; for each length l = 1..16 the next counts[l]
+ * values get consecutive codes, then code <<= 1.  Bits are read MSB first; a byte FF followed by 00 is the data byte
+ * FF, FF followed by anything else ends the segment's data.  Per block: the DC symbol s from the component's DC
+ * table, diff = EXTEND(s bits), the component's predictor += diff is coefficient 0; then k = 1 and until k = 64: the AC
+ * symbol rs, r = rs >> 4, s = rs & 15; s != 0: k += r, coefficient k = EXTEND(s bits), k += 1; s == 0 and r == 15:
+ * k += 16; s == 0 otherwise: the block ends.  EXTEND(v of s bits) = v < 2^(s-1) ? v - 2^s + 1 : v.  Coefficient k sits
+ * at zigzag position k and is multiplied by byte k of the component's table.  With DRI, every `restart` MCUs a new
+ * segment begins: the rest of the byte is dropped, the marker RSTn (FF D0+n, n counting the markers modulo 8) is
+ * expected, and the predictors return to 0.  A segment is decoded by one lane from its first byte (the host finds the
+ * markers); it ends at the two bytes of the next segment's marker, the last one at the stream's end.
+ *
+ * IDCT: libjpeg's accurate integer one (CONST_BITS 13, PASS1_BITS 2) in 64-bit integers.  On 8 values c0..c7:
+ *   z1 = (c2 + c6) * 4433, t2 = z1 - c6 * 15137, t3 = z1 + c2 * 6270, t0 = (c0 + c4) << 13, t1 = (c0 - c4) << 13,
+ *   t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+ *   a0 = c7, a1 = c5, a2 = c3, a3 = c1; z1 = a0 + a3, z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3, z5 = (z3 + z4) * 9633;
+ *   a0 *= 2446, a1 *= 16819, a2 *= 25172, a3 *= 12299, z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5,
+ *   z4 = z4 * -3196 + z5; a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4;
+ *   outputs 0..7 = t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3.
+ * Columns first, each output (x + 2^10) >> 11 kept as int32; then rows, (x + 2^17) >> 18; add 128, clamp to 0..255.
+ *
+ * Upsampling of Cb and Cr to the luma grid, with n the real width of the chroma plane.  n <= 2, or sampling (1,1):
+ * replication, out(x, y) = s(x / hs, y / vs).  (2,1), n > 2 ("fancy"): out[2i] = (3 s[i] + s[i-1] + 1) >> 2,
+ * out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2, out[0] = s[0], out[2n-1] = s[n-1].  (2,2), n > 2: for output row y the
+ * chroma row r = y / 2 and its neighbour r - 1 (y even) or r + 1 (y odd), kept inside the real rows; cs = 3 * row r
+ * + the neighbour; out[2i] = (3 cs[i] + cs[i-1] + 8) >> 4, out[2i+1] = (3 cs[i] + cs[i+1] + 7) >> 4,
+ * out[0] = (4 cs[0] + 8) >> 4, out[2n-1] = (4 cs[n-1] + 7) >> 4.  The result is cropped to W x H.
+ *
+ * Colour.  One component: R = G = B = Y.  Three: F(x) = int(x * 65536 + 0.5), cb -= 128, cr -= 128,
+ *   R = Y + ((F(1.402) cr + 32768) >> 16), B = Y + ((F(1.772) cb + 32768) >> 16),
+ *   G = Y + ((-F(0.34414) cb + 32768 - F(0.71414) cr) >> 16), arithmetic shifts, each clamped to 0..255.
+ *
+ * Bad streams.  Every field of a record is checked against the byte buffer, the output and the workspace before it is
+ * used; every read of a stream against the stream's (segment's) end; every write lands inside the image's own
+ * regions.  An image that fails (BASD_JPEG_BAD_* above) has an all-zero output (nothing is written for it where its
+ * output range itself is out of bounds), its code in its status word and the code's bit in `status`; the other images
+ * are unaffected.
+ *
+ * Launches (THREE per batch, whatever B; no allocation, no memset, no wait for the device):
+ *   entropy   one workgroup of 64 lanes per image: lanes 0 .. 2 ncomp - 1 build the look-ahead tables (9 bits) of the
+ *             components' DHT tables in LDS, then lane l decodes segments l, l + 64, ...; a block is assembled in LDS
+ *             and stored as 64 int16 in the stream's zigzag order;
+ *   idct      one lane per block: dequantise, IDCT, 8 rows of 8 bytes into the block's place in its component plane;
+ *   pixels    one lane per output pixel: upsampling taps, colour conversion, crop, 3 bytes; a raw record's pixels
+ *             are copied, a failed image's are zero.
+ * B == 0 launches nothing; B > BASD_JPEG_MAX_BATCH, misaligned or overlapping buffers, a workspace shorter than
+ * basd_jpeg_status_bytes(B) or negative counts return BASD_EINVAL before anything is launched. */
+int basd_jpeg_decode(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
+                     const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status, long max_blocks,
+                     long max_pixels, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,157 @@
+"""The decode of one batch of 256 JPEG files of 500 x 375 (quality 90, 4:2:0) on the device (basd_amd.jpeg, three
+launches) beside Pillow's decode of the same files in 1 and in 16 processes on the same machine.
+usage: jpeg_bench.py [--batch 256] [--windows 5] [--per-window 10] [--processes 16] [--device-only]
+(--device-only: no worker processes and no Pillow timing, for a run under a profiler)
+Where Pillow is importable the files are encoded with it (16 different pictures, repeated); otherwise the largest
+stream of tests/golden/jpeg_decode.npz is repeated and only the device is timed (the output says so).  The windows of
+the device and the Pillow runs alternate; the figures are medians over the windows."""
+import argparse
+import io
+import json
+import multiprocessing
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "vit-inductive-bias-distillation_amd"))
+
+
+def have_pillow() -> bool:
+    try:
+        import PIL.Image  # noqa: F401
+    except ImportError:
+        return False
+    return True
+
+
+def make_streams(batch: int, width: int = 500, height: int = 375, quality: int = 90, distinct: int = 16):
+    """(files, how they were made): ``batch`` JPEG files.  With Pillow: ``distinct`` seeded pictures (smooth colour
+    fields, edges and sensor-like noise) encoded at ``quality`` with 4:2:0, repeated; without: the largest recorded
+    stream repeated."""
+    if not have_pillow():
+        g = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_decode.npz"), allow_pickle=False)
+        name = max((n for n in g["names"] if not str(n).startswith("fallback_")), key=lambda n: g[f"stream_{n}"].size)
+        return [g[f"stream_{name}"].tobytes()] * batch, f"no Pillow here: the recorded stream {name} repeated"
+    from PIL import Image
+    rng = np.random.default_rng(5)
+    files = []
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+    for _ in range(distinct):
+        planes = []
+        for _c in range(3):
+            field = sum(rng.uniform(20, 60) * np.sin(xx * rng.uniform(0.005, 0.08) + yy * rng.uniform(0.005, 0.08)
+                                                     + rng.uniform(0, 6.3)) for _k in range(4))
+            edges = 60.0 * ((xx * rng.uniform(-1, 1) + yy * rng.uniform(-1, 1)) % rng.uniform(40, 160) < 20)
+            planes.append(128 + field + edges + rng.normal(0, 11, size=field.shape))
+        out = io.BytesIO()
+        Image.fromarray(np.clip(np.stack(planes, axis=2), 0, 255).astype(np.uint8)).save(
+            out, format="JPEG", quality=quality, subsampling=2)
+        files.append(out.getvalue())
+    return [files[i % distinct] for i in range(batch)], \
+        f"Pillow {__import__('PIL').__version__}: {distinct} pictures of {width} x {height}, quality {quality}, 4:2:0"
+
+
+def _pillow_pixels(data: bytes) -> np.ndarray:
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as img:
+        return np.asarray(img.convert("RGB"))
+
+
+def _pillow_decode(data: bytes) -> int:
+    return _pillow_pixels(data).size
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--per-window", type=int, default=10)
+    ap.add_argument("--processes", type=int, default=16)
+    ap.add_argument("--device-only", action="store_true")
+    args = ap.parse_args()
+    files, how = make_streams(args.batch)
+    pillow = have_pillow()
+    timed_pillow = pillow and not args.device_only
+    # the worker processes exist before this process opens the GPU, and never open it themselves
+    pool = multiprocessing.get_context("fork").Pool(args.processes) if timed_pillow else None
+    import torch
+    from basd_amd.jpeg import JpegDecoder, decode_reference, pack_jpegs
+    dev = torch.device("cuda", 0)
+    t0 = time.perf_counter()
+    packed = pack_jpegs(files)
+    pack_ms = (time.perf_counter() - t0) * 1e3
+    assert packed.fallbacks == 0
+    pinned = packed.pin_memory()
+    decoder = JpegDecoder(dev)
+    batch = pinned.to(dev, non_blocking=True)
+    for _ in range(3):
+        ragged = decoder(batch)
+    torch.cuda.synchronize()
+    assert decoder.status() == 0
+    check = [0, args.batch // 2, args.batch - 1]
+    for i in check:
+        want = _pillow_pixels(files[i]) if pillow else decode_reference(files[i])
+        assert np.array_equal(ragged.image(i).cpu().numpy(), want), i
+    stream_bytes = sum(len(f) for f in files)
+    info = {"case": "the batch", "files": how, "batch": args.batch, "stream_bytes": stream_bytes,
+            "decoded_bytes": packed.out_bytes, "workspace_bytes": packed.workspace_bytes,
+            "blocks_per_image": packed.max_blocks, "pack_jpegs_ms": round(pack_ms, 2)}
+    print(json.dumps(info))
+    launches, calls, uploads, one, many = [], [], [], [], []
+    for _ in range(args.windows):
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        start.record()
+        for _ in range(args.per_window):
+            decoder(batch)
+        stop.record()
+        torch.cuda.synchronize()
+        calls.append((time.perf_counter() - t0) * 1e3 / args.per_window)
+        launches.append(start.elapsed_time(stop) / args.per_window)
+        t0 = time.perf_counter()
+        for _ in range(args.per_window):
+            pinned.to(dev, non_blocking=True)
+        torch.cuda.synchronize()
+        uploads.append((time.perf_counter() - t0) * 1e3 / args.per_window)
+        if timed_pillow:
+            t0 = time.perf_counter()
+            for f in files:
+                _pillow_decode(f)
+            one.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            pool.map(_pillow_decode, files, chunksize=max(1, args.batch // (4 * args.processes)))
+            many.append((time.perf_counter() - t0) * 1e3)
+    if pool is not None:
+        pool.close()
+        pool.join()
+    assert decoder.status() == 0
+
+    def line(case, ms):
+        med = statistics.median(ms)
+        row = {"case": case, "ms": [round(v, 3) for v in ms], "median_ms": round(med, 3),
+               "spread_ms": round(max(ms) - min(ms), 3), "images_per_s": round(args.batch / med * 1e3)}
+        print(json.dumps(row))
+        return med
+
+    device_ms = line("device decode, three launches (device events)", launches)
+    line("JpegDecoder.__call__ (table copied, launched, waited for)", calls)
+    line("upload of the packed files (pinned, one copy)", uploads)
+    if timed_pillow:
+        one_ms = line("Pillow, 1 process", one)
+        many_ms = line(f"Pillow, {args.processes} processes (results not sent back)", many)
+        print(f"\n  device {device_ms:.3f} ms per batch of {args.batch}; Pillow {one_ms:.1f} ms in 1 process, {many_ms:.1f} ms "
+              f"in {args.processes}: the device decode is faster by a factor of {one_ms / device_ms:.1f} and "
+              f"{many_ms / device_ms:.1f}; images {check} compared byte for byte")
+    else:
+        print(f"\n  device {device_ms:.3f} ms per batch of {args.batch}; Pillow not timed; images {check} compared "
+              f"with {'Pillow' if pillow else 'decode_reference'} byte for byte")
+
+
+if __name__ == "__main__":
+    main()

@@ -6,7 +6,10 @@ usage: trainer_step_bench.py [--batch 256] [--steps 8] [--dtype bf16|fp32] [--op
 fused: basd_amd.attention on each block's own qkv output, one launch per layer)
 [--uint8]  (the loader's contract of mixup="fused" + image_stats: both batches arrive as bytes and are converted and
 normalised inside the fused launches)  [--trivial-augment]  (with --uint8: the flip and TrivialAugmentWide of the augmented
-batch on the device, basd_amd.trivial_augment, one launch per batch ahead of the mixer)"""
+batch on the device, basd_amd.trivial_augment, one launch per batch ahead of the mixer)
+[--resize-crop]  (with --uint8: the batch is a pinned RaggedBatch of 500 x 375 decoded images, uploaded inside the step;
+basd_amd.resize makes both views, one launch)  [--jpeg-decode]  (with --resize-crop: the batch is a pinned JpegBatch of
+the same pictures as JPEG files (tools/jpeg_bench.make_streams), decoded by basd_amd.jpeg ahead of the resize launch)"""
 import argparse, os, sys, time
 from types import SimpleNamespace
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,11 +29,22 @@ ap.add_argument("--teacher", default="resnet50", choices=["resnet50", "vit_b"])
 ap.add_argument("--attn-capture", default="torch", choices=["torch", "fused"])
 ap.add_argument("--uint8", action="store_true")
 ap.add_argument("--trivial-augment", action="store_true")
+ap.add_argument("--resize-crop", action="store_true")
+ap.add_argument("--jpeg-decode", action="store_true")
 args = ap.parse_args()
 if args.uint8 and args.mixup != "fused":
     ap.error("--uint8 needs --mixup fused")
 if args.trivial_augment and not args.uint8:
     ap.error("--trivial-augment needs --uint8")
+if args.resize_crop and not args.uint8:
+    ap.error("--resize-crop needs --uint8")
+if args.jpeg_decode and not args.resize_crop:
+    ap.error("--jpeg-decode needs --resize-crop")
+files = None
+if args.resize_crop:
+    # made before the GPU is opened (the pictures are encoded, and for --resize-crop decoded, with Pillow on the host)
+    from tools import jpeg_bench
+    files, how_made = jpeg_bench.make_streams(args.batch)
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 student = SM.StockViT().to(dev)                      # DeiT-S
@@ -39,14 +53,17 @@ if args.teacher == "vit_b":
 else:
     teacher = SM.make_teacher(SM.StockResNet().to(dev), 224)
 cfg = SimpleNamespace(training=SimpleNamespace(label_smoothing=0.1, learning_rate=1e-3, weight_decay=0.05),
-                      basd=SimpleNamespace(num_extraction_points=4), model=SimpleNamespace(num_classes=1000))
+                      basd=SimpleNamespace(num_extraction_points=4),
+                      model=SimpleNamespace(num_classes=1000, vit=SimpleNamespace(img_size=224)),
+                      data=SimpleNamespace(eval_crop_ratio=0.875))
 torch.manual_seed(42)
 ac = torch.bfloat16 if args.dtype == "bf16" else None
 tr = T.Trainer(student, cfg, teacher, student_info=SM.probe_model(student, 224), autocast_dtype=ac,
                mixup=True if args.mixup == "torch" else "fused", optimizer=args.optimizer,
                attn_capture=args.attn_capture,
                image_stats={"clean": ((0.5,) * 3, (0.25,) * 3), "augmented": ((0.5,) * 3, (0.25,) * 3)} if args.uint8 else None,
-               mix_dtype=ac if args.uint8 else None, trivial_augment=args.trivial_augment)
+               mix_dtype=ac if args.uint8 else None, trivial_augment=args.trivial_augment,
+               resize_crop=args.resize_crop, jpeg_decode=args.jpeg_decode)
 g = torch.Generator().manual_seed(1)
 B = args.batch
 # images with per-image structure (a random colour cast + noise) so that the teacher features are not pure noise
@@ -57,6 +74,13 @@ if args.uint8:
     # the same images as bytes (x = 255 (0.5 + 0.25 v), clamped); the parts below keep the float batch
     as_bytes = lambda t: (t * 0.25 + 0.5).clamp_(0, 1).mul_(255).to(torch.uint8)
     step_batch = {"clean": as_bytes(imgs), "augmented": as_bytes(imgs.flip(3)), "label": batch["label"]}
+if args.jpeg_decode:
+    from basd_amd.jpeg import pack_jpegs
+    step_batch = {"images": pack_jpegs(files).pin_memory(), "label": batch["label"]}
+elif args.resize_crop:
+    from basd_amd.jpeg import pillow_fallback
+    from basd_amd.resize import pack_images
+    step_batch = {"images": pack_images([pillow_fallback(f) for f in files]).pin_memory(), "label": batch["label"]}
 
 
 def timed(fn, n):
@@ -102,6 +126,7 @@ def loss_only():
 loss_only()
 l_ms = timed(loss_only, args.steps)
 print({"batch": B, "dtype": args.dtype, "optimizer": args.optimizer, "mixup": args.mixup, "teacher": args.teacher,
-       "attn_capture": args.attn_capture, "uint8": args.uint8, "trivial_augment": args.trivial_augment, "step_ms": round(step_ms, 2), "images_per_s": round(B / step_ms * 1e3, 1),
+       "attn_capture": args.attn_capture, "uint8": args.uint8, "trivial_augment": args.trivial_augment, "resize_crop": args.resize_crop,
+       "jpeg_decode": args.jpeg_decode, "step_ms": round(step_ms, 2), "images_per_s": round(B / step_ms * 1e3, 1),
        "student_fwd_nograd_ms": round(s_ms, 2), "teacher_fwd_ms": round(t_ms, 2), "loss_fwd_bwd_ms": round(l_ms, 2),
        "loss_share": round(l_ms / step_ms, 3), "loss": float(out["loss"]), "ranks": dict(tr.basd_loss.layer_selector.subspace_ranks)})

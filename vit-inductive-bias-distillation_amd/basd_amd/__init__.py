@@ -17,6 +17,8 @@ Sub-modules:
                launch per batch
   ``resize``   ``ResizeCrop`` / ``pack_images`` / ``collate_ragged`` / ``draw_crop_params``: Pillow-exact crops and resizes
                of ragged batches of decoded uint8 images, both views in one launch
+  ``jpeg``     ``JpegDecoder`` / ``pack_jpegs`` / ``collate_jpeg`` / ``parse_jpeg``: Pillow-exact baseline JPEG decoding of a
+               batch of files' bytes into a ragged batch, three launches per batch
   ``_launch``  what those one-launch stages share on the host: argument checks, dtype codes, the record-table uploader
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """
@@ -26,6 +28,9 @@ from .attention import attn_importance  # noqa: E402
 from .trivial_augment import AugmentParams, TrivialAugment, draw_augment_params  # noqa: E402
 from .resize import (CropParams, RaggedBatch, ResizeCrop, collate_ragged, draw_crop_params,  # noqa: E402
                      eval_window, pack_images)
+from .jpeg import (JpegBatch, JpegDecoder, UnsupportedJpeg, collate_jpeg, decode_reference,  # noqa: E402
+                   pack_jpegs, parse_jpeg)
 
 __all__ = ["attn_importance", "AugmentParams", "TrivialAugment", "draw_augment_params", "CropParams", "RaggedBatch",
-           "ResizeCrop", "collate_ragged", "draw_crop_params", "eval_window", "pack_images"]
+           "ResizeCrop", "collate_ragged", "draw_crop_params", "eval_window", "pack_images", "JpegBatch", "JpegDecoder",
+           "UnsupportedJpeg", "collate_jpeg", "decode_reference", "pack_jpegs", "parse_jpeg"]

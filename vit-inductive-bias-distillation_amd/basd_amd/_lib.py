@@ -122,6 +122,8 @@ SIGNATURES = {
     "basd_channel_stats": [vp, i32, i64, i32, i64, vp, i32, vp],
     "basd_trivial_augment": [vp, vp, i32, i32, i32, i32, vp, vp, vp],
     "basd_resize_crop": [vp, i64, vp, i32, i32, i32, i32, vp, vp, i32, vp],
+    "basd_jpeg_status_bytes": [i32],
+    "basd_jpeg_decode": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp],
 }
 
 class ProcrustesArgs(C.Structure):
@@ -170,7 +172,7 @@ EINVAL, EUNSUPPORTED = -1, -2        # BASD_EINVAL / BASD_EUNSUPPORTED of includ
 # sizing helpers declared `long` in include/basd_hip.h
 LONG_RESULTS = {"basd_tridiag_workspace_bytes", "basd_jacobi_twopass_workspace_bytes",
                 "basd_mix_grad_tokens_scratch_floats", "basd_teacher_center_stream_scratch_floats",
-                "basd_rank_certificate_scratch_bytes", "basd_sfadamw_launches"}
+                "basd_rank_certificate_scratch_bytes", "basd_sfadamw_launches", "basd_jpeg_status_bytes"}
 
 _lock = threading.Lock()
 _lib = None

@@ -110,7 +110,8 @@ def _label_smoothing_of(criterion) -> float:
 
 @torch.no_grad()
 def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_classes: int, valid_indices=None,
-                   distributed: bool = False, image_stats=None, input_dtype=None, resize_crop=None) -> dict:
+                   distributed: bool = False, image_stats=None, input_dtype=None, resize_crop=None,
+                   jpeg_decode=None) -> dict:
     """The reference's ``evaluate_model``: batches are dicts with ``pixel_values`` and ``label``; returns ``val_acc``,
     ``val_acc_top5`` (percent) and ``loss`` (mean of ``criterion`` over the samples); fewer than 5 evaluated classes
     raise ``ValueError``.  ``distributed=True``: every rank iterates its own shard and the counts are summed over the
@@ -122,11 +123,16 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
     whatever ``image_stats`` and ``input_dtype`` say.
     ``resize_crop``: a ``basd_amd.resize.ResizeCrop``; with it a batch may carry ``images`` (a ``RaggedBatch`` of decoded
     images, ``collate_fn=collate_ragged``) instead of ``pixel_values``: one launch makes the clean view (``Resize ->
-    CenterCrop``), which then takes the uint8 path above, so ``image_stats`` is needed (``ValueError`` otherwise)."""
+    CenterCrop``), which then takes the uint8 path above, so ``image_stats`` is needed (``ValueError`` otherwise).
+    ``jpeg_decode``: a ``basd_amd.jpeg.JpegDecoder`` (it needs ``resize_crop``); with it ``images`` may be a ``JpegBatch``
+    of the files' bytes (``collate_fn=collate_jpeg``), decoded on the device ahead of the resize launch."""
     label_smoothing = _label_smoothing_of(criterion)
     if resize_crop is not None and image_stats is None:
         raise ValueError("resize_crop needs image_stats=(mean, std): its uint8 batches are converted and normalised on "
                          "the device; got image_stats=None")
+    if jpeg_decode is not None and resize_crop is None:
+        raise ValueError("jpeg_decode needs resize_crop=ResizeCrop(...): the decoded images are a ragged batch; got "
+                         "resize_crop=None")
     model.eval()
     device = next(model.parameters()).device
     acc = EvalAccumulator(num_classes, valid_indices=valid_indices, label_smoothing=label_smoothing, top_k=5,
@@ -140,7 +146,12 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
         if "images" in batch and "pixel_values" not in batch:
             if resize_crop is None:
                 raise TypeError("a batch of decoded 'images' needs resize_crop=ResizeCrop(...); got resize_crop=None")
-            inputs = resize_crop(batch["images"].to(device, non_blocking=True), views=("clean",))["clean"]
+            images = batch["images"].to(device, non_blocking=True)
+            if jpeg_decode is not None:
+                from .jpeg import JpegBatch
+                if isinstance(images, JpegBatch):
+                    images = jpeg_decode(images)
+            inputs = resize_crop(images, views=("clean",))["clean"]
         else:
             inputs = batch["pixel_values"]
         if inputs.dtype == torch.uint8 and converter is None:

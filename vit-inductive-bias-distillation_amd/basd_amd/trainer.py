@@ -102,12 +102,15 @@ class Trainer:
     ``"clean"`` / ``"augmented"``, and one HIP launch resizes and crops the clean view (``Resize -> CenterCrop``) and the
     augmented one (``RandomResizedCrop``) to ``config.model.vit.img_size`` with ``config.data.eval_crop_ratio``; it needs
     ``mixup="fused"`` and ``image_stats``.  The crops are drawn per step on the global CPU generator, or taken from the
-    batch's optional ``"crop_params"`` entry (a ``CropParams``).  ``prepare_views(batch)`` returns the two batches."""
+    batch's optional ``"crop_params"`` entry (a ``CropParams``).  ``prepare_views(batch)`` returns the two batches.
+    ``jpeg_decode``: ``True`` (it needs ``resize_crop``) lets the batch's ``"images"`` be a ``JpegBatch`` of the files' bytes
+    (the loader does not decode, ``collate_fn=collate_jpeg``): three launches of ``basd_amd.jpeg.JpegDecoder`` decode it
+    into the ``RaggedBatch`` the resize launch takes; a ``RaggedBatch`` is taken as before."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
-                 resize_crop: bool = False) -> None:
+                 resize_crop: bool = False, jpeg_decode: bool = False) -> None:
         self.config = config
         self.device = next(student_model.parameters()).device
         self.criterion = nn.CrossEntropyLoss(label_smoothing=config.training.label_smoothing)
@@ -165,6 +168,13 @@ class Trainer:
             self._require_fused("resize_crop needs", "it hands its uint8 batches to the fused launches")
             from .resize import ResizeCrop
             self._resizer = ResizeCrop(config.model.vit.img_size, config.data.eval_crop_ratio, device=self.device)
+        self._decoder = None
+        if jpeg_decode:
+            if not resize_crop:
+                raise ValueError("jpeg_decode needs resize_crop=True (the decoded images are a ragged batch, which the "
+                                 "resize launch takes); got resize_crop=False")
+            from .jpeg import JpegDecoder
+            self._decoder = JpegDecoder(self.device)
         self.best_val_acc = 0.0
         self.metrics_history = defaultdict(list)
         self._params = [p for p in student_model.parameters() if p.requires_grad]
@@ -202,6 +212,10 @@ class Trainer:
             return batch["clean"].to(dev, non_blocking=True), batch["augmented"].to(dev, non_blocking=True)
         from .resize import RaggedBatch
         images = batch.get("images")
+        if self._decoder is not None:
+            from .jpeg import JpegBatch
+            if isinstance(images, JpegBatch):
+                images = self._decoder(images.to(dev, non_blocking=True))
         if not isinstance(images, RaggedBatch):
             raise TypeError("resize_crop works on decoded images (the loader decodes, nothing else): the batch needs "
                             f"'images', a RaggedBatch (collate_fn=collate_ragged); got {sorted(batch)}")
@@ -301,7 +315,8 @@ class Trainer:
         with more than one rank exists.  With ``image_stats`` the validation loader may hand over uint8
         ``pixel_values``: they are normalised on the device with the ``augmented`` statistics -- the dataset's own, which
         the reference's validation loader uses too (datasets.py:168-175) -- and written as ``mix_dtype``.  With
-        ``resize_crop`` it may hand over ``images`` (a ``RaggedBatch``) instead: they are resized and cropped first.  Has the
+        ``resize_crop`` it may hand over ``images`` (a ``RaggedBatch``) instead: they are resized and cropped first (with
+        ``jpeg_decode`` a ``JpegBatch``: decoded, then resized and cropped).  Has the
         signature ``train(..., evaluate=)`` expects: ``trainer.train(train_loader, val_loader,
         evaluate=trainer.evaluate)``."""
         from .evaluation import evaluate_model
@@ -309,7 +324,7 @@ class Trainer:
         stats = None if self.image_stats is None else self.image_stats["augmented"]
         return evaluate_model(model, val_loader, self.criterion, num_classes=self.config.model.num_classes,
                               distributed=distributed, image_stats=stats, input_dtype=self.mix_dtype,
-                              resize_crop=self._resizer)
+                              resize_crop=self._resizer, jpeg_decode=self._decoder)
 
     def train(self, train_loader, val_loader=None, start_epoch: int = 0, *, evaluate=None, on_epoch_end=None) -> dict:
         """The reference's epoch loop (trainer.py:171-216): ``_train_epoch``, validation, ``metrics_history``,
