@@ -1563,8 +1563,15 @@ __global__ void __launch_bounds__(64) tridiag_invit_kernel(const float* __restri
     }
     // inverse iteration: two solves with slagts-style pivot perturbation.  The shift is an eigenvalue to a few
     // eps ||T||, so the first solve already amplifies the wanted direction by ~1/eps; the iterate enters each
-    // solve with unit 2-norm times n ||T|| eps (sstein's scaling), folded into the forward sweep.
-    const float s0 = (float)n * tnorm * eps;
+    // solve with unit 2-norm times n ||T|| eps (sstein's scaling), folded into the forward sweep (n times the floor
+    // for T = 0, whose iterates would otherwise all be zero vectors).
+    const float s0 = (float)n * tol;
+    // As in slagts a pivot is only perturbed where the quotient would leave the range: the floor is eps^2 ||T|| and
+    // the quotient is clamped to 1e16 (the squares stay finite for n <= 1024).  Replacing every pivot below eps ||T||
+    // also replaced off-diagonal entries of that size which an interchange had made pivots; the multiplier of such an
+    // interchange, up to ||T|| / (shift - eigenvalue), carried the change into the row of the large entry: the
+    // vectors of an (n - 1)-fold eigenvalue of ones + 2 I came out with 3e-5 of the top eigenvector at n = 45.
+    const float pfloor = fmaxf(eps * tol, 1e-37f);
     {
         float ss = 0.f;
         for (int i = 0; i < n; ++i) ss = fmaf(x[i * vpw], x[i * vpw], ss);
@@ -1584,13 +1591,13 @@ __global__ void __launch_bounds__(64) tridiag_invit_kernel(const float* __restri
             prev = next;
         }
         x[(n - 1) * vpw] = prev;
-        // back substitution (U); |x| <= ~n here, so the squares cannot overflow
+        // back substitution (U); |x| <= 1e16 here, so the squares cannot overflow
         float x1 = 0.f, x2 = 0.f, ss = 0.f;
         for (int i = n - 1; i >= 0; --i) {
             float tmp = x[i * vpw] - b[i * vpw] * x1 - d2[i * vpw] * x2;    // b / d2 are 0 past the end
             float ak = a[i * vpw];
-            if (fabsf(ak) < tol) ak = copysignf(tol, ak == 0.f ? 1.f : ak);
-            tmp *= __builtin_amdgcn_rcpf(ak);
+            if (fabsf(ak) < pfloor) ak = copysignf(pfloor, ak == 0.f ? 1.f : ak);
+            tmp = __builtin_amdgcn_fmed3f(tmp * __builtin_amdgcn_rcpf(ak), -1e16f, 1e16f);
             x[i * vpw] = tmp;
             ss = fmaf(tmp, tmp, ss);
             x2 = x1;
@@ -1641,7 +1648,7 @@ __global__ void __launch_bounds__(1024) cluster_orth_kernel(const float* __restr
     int s0 = 0;
     while (s0 < k) {
         int s1 = s0 + 1;                                            // cluster [s0, s1): consecutive gaps below 1e-3 ||T||
-        while (s1 < k && lam[s1 - 1] - lam[s1] < 1e-3f * tnorm) ++s1;
+        while (s1 < k && lam[s1 - 1] - lam[s1] <= 1e-3f * tnorm) ++s1;      // <=: T = 0 is one cluster
         if (s1 - s0 > 1) {
             for (int p0 = s0; p0 < s1; p0 += PW) {
                 const int np = min(PW, s1 - p0);
