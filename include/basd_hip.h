@@ -189,6 +189,12 @@ int basd_tridiag_tuning(int members, int pad, int lag, int threads, int tail, in
 /* All eigenvalues (descending) of the tridiagonals by Sturm-sequence bisection. */
 int basd_tridiag_eigenvalues(const float* d, const float* e, int n, int batch, float* vals_desc, hipStream_t stream);
 
+/* The leading eigenvalues only (layer_selector.py:36-37, :92: S[:k] and Vh[:k] are all that is read of a spectrum once
+ * the ranks are known): writes elements [0, min(n, 64 ceil(k / 64))) of every row of vals_desc (row stride n) with the
+ * bits basd_tridiag_eigenvalues writes there, and leaves the rest of the row untouched.  k > 0; a k past n is taken as n. */
+int basd_tridiag_eigenvalues_leading(const float* d, const float* e, int n, int k, int batch, float* vals_desc,
+                                     hipStream_t stream);
+
 /* out (batch, k_stride, n) rows = Q x (transpose = 0) or Q^T x (transpose = 1) for the rows of x (batch, k, n), Q the
  * product of the reflectors of basd_tridiag.  With basd_tridiag_shifted_solve this gives (A - lambda I)^{-1} on the
  * orthogonal complement of the leading eigenvectors: the part of the backward of `torch.linalg.svd(...).Vh[:k]`

@@ -47,6 +47,7 @@ SIGNATURES = {
     "basd_event_destroy": [vp],
     "basd_stream_wait_event": [vp, vp],
     "basd_tridiag_eigenvalues": [vp, vp, i32, i32, vp, vp],
+    "basd_tridiag_eigenvalues_leading": [vp, vp, i32, i32, i32, vp, vp],
     "basd_tridiag_apply_q": [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp],
     "basd_tridiag_shifted_solve": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],
     "basd_tridiag_mp_rank": [vp, vp, i32, i32, f64, i32, vp, vp, vp, vp, vp],

@@ -207,7 +207,8 @@ int basd_selector_chain_tail(const BasdSelectorChain* a, int kmax, int exact_k) 
     const float* tz = a->tau + (long)L * n;
     const float* vz = a->vh + (long)L * nn;
     float* lam = a->vals + (long)L * n;
-    BASD_TRY(basd_tridiag_eigenvalues(dz, ez, n, L + E, lam, st));
+    // lam[0:kmax] is all that is read below (inverse-iteration shifts, clusters, chain_sw_kernel)
+    BASD_TRY(basd_tridiag_eigenvalues_leading(dz, ez, n, kmax, L + E, lam, st));
     BASD_MARK(a->tm_spec, st);
     // rows of vecs: (L + E, kmax, n) -- teacher bases first, then Vt_s[:kmax] of every student layer
     BASD_TRY(basd_tridiag_eigenvectors(dz, ez, tz, vz, lam, n, kmax, L + E, a->zv, a->vecs, kmax, st));

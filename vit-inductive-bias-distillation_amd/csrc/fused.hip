@@ -48,10 +48,11 @@ __global__ void __launch_bounds__(256) uwso_combine_kernel(const float* __restri
 __global__ void __launch_bounds__(256) scale_unless_one_kernel(float* __restrict__ x, long count4, long count,
                                                                const float* __restrict__ num,
                                                                const float* __restrict__ den) {
+    // grid-stride over a few workgroups per CU: when nothing is to be scaled (the common case) a handful of
+    // workgroups read the factor once and leave, instead of one workgroup per 1024 elements
     const float f = den ? num[0] / den[0] : num[0];
     if (f == 1.f) return;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < count4) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count4; i += (long)gridDim.x * 256) {
         float4 v = ((float4*)x)[i];
         v.x *= f; v.y *= f; v.z *= f; v.w *= f;
         ((float4*)x)[i] = v;
@@ -66,7 +67,8 @@ extern "C" {
 int basd_scale_unless_one(float* x, long count, const float* num, const float* den, hipStream_t stream) {
     BASD_CHECK_ARG(x && num && count > 0 && ((uintptr_t)x & 15) == 0);
     const long count4 = count / 4;
-    basd::scale_unless_one_kernel<<<(unsigned)((count4 + 255) / 256 + (count4 == 0)), 256, 0, stream>>>(x, count4, count, num, den);
+    const long groups = (count4 + 255) / 256 + (count4 == 0);
+    basd::scale_unless_one_kernel<<<(unsigned)(groups < 1024 ? groups : 1024), 256, 0, stream>>>(x, count4, count, num, den);
     BASD_RETURN_LAST();
 }
 

@@ -1179,9 +1179,11 @@ __global__ void __launch_bounds__(64 * PK_WAVES) tridiag_packed_kernel(float* __
     auto next_reflector = [&](int jl, bool last, const float (&cn)[CH], const float (&uc)[CH], const float (&wn)[CH],
                               float dnew) {
         const int r0 = jl + 1;
+        // columns c = pl + 64 k are compared as pl against the wave-uniform r0 - 64 k: the six c are not kept in
+        // registers across the pass (256 of 256 are taken; with them the compiler spilled four values to scratch)
         float part2 = 0.f;
 #pragma unroll
-        for (int k = 0; k < CH; ++k) part2 = (pl + 64 * k > r0) ? fmaf(cn[k], cn[k], part2) : part2;
+        for (int k = 0; k < CH; ++k) part2 = (pl > r0 - 64 * k) ? fmaf(cn[k], cn[k], part2) : part2;
         const float alpha = pick(cn, r0 < PK_NMAX ? r0 : PK_NMAX - 1);
         const float xn2 = wave_sum(part2);
         const bool live = !last && xn2 > 0.f;
@@ -1191,8 +1193,8 @@ __global__ void __launch_bounds__(64 * PK_WAVES) tridiag_packed_kernel(float* __
         float un[CH];
 #pragma unroll
         for (int k = 0; k < CH; ++k) {
-            const int c = pl + 64 * k;
-            un[k] = last ? 0.f : (c < r0 ? 0.f : (c == r0 ? 1.f : cn[k] * scal));
+            const int rk_ = r0 - 64 * k;
+            un[k] = last ? 0.f : (pl < rk_ ? 0.f : (pl == rk_ ? 1.f : cn[k] * scal));
             pub[24 * k] = uc[k];
             pub[24 * k + 8] = wn[k];
             pub[24 * k + 16] = un[k];
@@ -1213,8 +1215,11 @@ __global__ void __launch_bounds__(64 * PK_WAVES) tridiag_packed_kernel(float* __
     // 64 columns per wave (one LDS read + one store each: nobody starts the next pass late)
     auto store_reflector = [&](int jl) {
         const int k = wave - 1;
-        if (k >= 0 && k < CH && lane + 64 * k < n)
-            Vz[(long)jl * n + lane + 64 * k] = ugather[24 * k];
+        if (k >= 0 && k < CH && lane + 64 * k < n) {
+            // the store address is the wave-uniform row start plus the lane: no per-lane 64-bit address in the loop
+            float* const vrow = Vz + ((long)jl * n + 64 * k);
+            vrow[(unsigned)lane] = ugather[24 * k];
+        }
     };
     if (wave == 0) {
         float cn[CH], zero[CH];
@@ -1279,6 +1284,14 @@ __global__ void __launch_bounds__(64 * PK_WAVES) tridiag_packed_kernel(float* __
             uc[0] = UC[0].x; uc[1] = UC[0].y; uc[2] = UC[1].x; uc[3] = UC[1].y; uc[4] = UC[2].x; uc[5] = UC[2].y;
             // the diagonal entry of the captured row (column r0: chunk r0 >> 6, lane pi(r0 & 63)): a uniform read
             const float cap_r0 = cap[(r0 >> 6) * 64 + pk_pi(r0 & 63)];
+            // the row sums and the captured row first: their latency passes under the reads of the partials
+            tri_f2 y2[3], capc2[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                // row sums of row c = 64 k + pi(lane): wave c & 7 = lane >> 3, index c >> 3 = 8 k + (lane & 7)
+                y2[q] = tri_f2{yrows[lane >> 3][16 * q + (lane & 7)], yrows[lane >> 3][16 * q + 8 + (lane & 7)]};
+                capc2[q] = tri_f2{cap[128 * q + lane], cap[128 * q + 64 + lane]};
+            }
             tri_f2 sc2[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
 #pragma unroll
             for (int w = 0; w < WAVES; ++w) {
@@ -1289,15 +1302,10 @@ __global__ void __launch_bounds__(64 * PK_WAVES) tridiag_packed_kernel(float* __
                 sc2[1] = pk_add(sc2[1], tri_f2{p0.z, p0.w});
                 sc2[2] = pk_add(sc2[2], p1);
             }
-            tri_f2 pc2[3], capc2[3];
+            tri_f2 pc2[3];
             const tri_f2 tau2 = {tau, tau};
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                // row sums of row c = 64 k + pi(lane): wave c & 7 = lane >> 3, index c >> 3 = 8 k + (lane & 7)
-                const tri_f2 y2 = {yrows[lane >> 3][16 * q + (lane & 7)], yrows[lane >> 3][16 * q + 8 + (lane & 7)]};
-                pc2[q] = pk_mul(tau2, pk_add(sc2[q], y2));
-                capc2[q] = tri_f2{cap[128 * q + lane], cap[128 * q + 64 + lane]};
-            }
+            for (int q = 0; q < 3; ++q) pc2[q] = pk_mul(tau2, pk_add(sc2[q], y2[q]));
             PK_STAMP(3);
             tri_f2 dot2 = {0.f, 0.f};
 #pragma unroll
@@ -2258,6 +2266,18 @@ int basd_tridiag_eigenvalues(const float* d, const float* e, int n, int batch, f
     BASD_CHECK_ARG(d && e && vals_desc && n > 0 && batch > 0);
     if (n > 8192) return BASD_EUNSUPPORTED;
     sturm_bisect_kernel<<<dim3((n + 63) / 64, batch), 1024, 0, stream>>>(d, e, n, vals_desc);
+    BASD_RETURN_LAST();
+}
+
+// The leading eigenvalues only: the same kernel on the first ceil(k / 64) workgroups of every matrix.  A row of 16 lanes
+// brackets its eigenvalue from the matrix's Gershgorin bounds and its own index, so the values written are those of the
+// full call, bit for bit; elements [min(n, 64 ceil(k / 64)), n) of every row of vals_desc (row stride n) are not touched.
+int basd_tridiag_eigenvalues_leading(const float* d, const float* e, int n, int k, int batch, float* vals_desc,
+                                     hipStream_t stream) {
+    BASD_CHECK_ARG(d && e && vals_desc && n > 0 && k > 0 && batch > 0);
+    if (n > 8192) return BASD_EUNSUPPORTED;
+    if (k > n) k = n;
+    sturm_bisect_kernel<<<dim3((k + 63) / 64, batch), 1024, 0, stream>>>(d, e, n, vals_desc);
     BASD_RETURN_LAST();
 }
 
