@@ -1027,6 +1027,48 @@ int basd_jpeg_decode(const unsigned char* src, long src_bytes, unsigned char* ou
                      const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status, long max_blocks,
                      long max_pixels, hipStream_t stream);
 
+/* The same decode with the entropy stage working INSIDE a segment in parallel (opt-in; basd_jpeg_decode above is the
+ * default and stays as it is).  Arguments, checks, workspace layout, record, status words and output bytes are those
+ * of basd_jpeg_decode: for every stream, intact or damaged, both give the same per-image status word and the same
+ * bytes (that is the contract; what holds the code to it is listed in DESIGN.md section 8).  Still three launches: a different entropy kernel, then the same idct and pixels kernels.
+ *
+ * sub_bytes: 0 (the built-in default, 128) or a multiple of 8 in BASD_JPEG_SUB_BYTES_MIN .. BASD_JPEG_SUB_BYTES_MAX;
+ * anything else returns BASD_EINVAL.
+ *
+ * Scheme.  One workgroup of 256 lanes per image.  An image of 64 segments or more is decoded a segment per lane as
+ * above.  Otherwise its segments are taken one after the other by the whole workgroup: the segment's coefficient area
+ * is zeroed, its bytes are cut into sub-sequences of sub_bytes, and these are worked through in chunks of 256 (one per
+ * lane); the exact decoder state, the number of blocks begun and the three DC predictors are carried from chunk to
+ * chunk.  In a chunk, (1) lane 0 decodes its sub-sequence from the carried state and every other lane from a guess (a
+ * block of component slot 0 begins at the sub-sequence's first byte), up to the first symbol that begins at or behind
+ * the sub-sequence's end, and keeps its exit state, the number of blocks that began and the sums of the DC differences
+ * per component; a bad code, an index past 63 or the end of the data is no error here, it leaves "no state".  (2) In
+ * rounds, each behind a barrier, a lane whose predecessor's exit state differs from the state it last entered with
+ * decodes again from it (from its own guess where the predecessor left no state); the rounds end when no lane decoded.
+ * After round n the first n + 1 sub-sequences are exact whatever the stream.  Huffman streams usually fall into step
+ * a few symbols to a kilobyte behind a wrong start and a chunk then takes a few rounds, but a periodic stream (a flat
+ * picture) can hold a wrong phase, and blocks without an end-of-block code hide the zigzag index, for ever.  So there
+ * are at most 64 such rounds; a chunk that has not settled by then is finished by one lane, which walks once through
+ * the sub-sequences behind the 65 exact ones while the other lanes wait.  A chunk thus takes AT MOST 66 rounds (the
+ * first pass, 64 rounds, the walk), its time stays within that of 256 passes over a sub-sequence, and termination does
+ * not rest on the stream.  (3) An exclusive prefix sum over the block counts and the DC sums, added to the carried
+ * ones, gives every lane its first block and its predictors.  (4) Every lane decodes once more from its now exact state
+ * and stores its coefficients one by one (a block that spans sub-sequences is filled by several lanes); no block at or
+ * past the segment's block count is begun, so padding is never decoded.  The segment is done when its last block has
+ * ENDED, not when it has begun: the handed-over state says so (more blocks begun than the segment has; or as many, and
+ * the zigzag index 0 or no state); a last block that begins in a chunk's last sub-sequence and runs on is finished,
+ * and an error in its rest is met, by the next chunk.  The last sub-sequence of a segment has no end
+ * and runs to the block count or to the error the serial decoder meets.  Of several lanes that fail the first in
+ * stream order gives the segment's code; an image's status is the largest of its segments' codes, as above.
+ * The exit state is canonical: it names the first byte of the stream of which no bit was taken (a stuffed 00 counts to
+ * its FF), the unread bits of the byte ahead of it, the block's slot in the MCU and the zigzag index, so two decoders
+ * at the same bit hand over equal states whatever their refills were. */
+#define BASD_JPEG_SUB_BYTES_MIN 8
+#define BASD_JPEG_SUB_BYTES_MAX 1024
+int basd_jpeg_decode_parallel(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
+                              const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status,
+                              long max_blocks, long max_pixels, int sub_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

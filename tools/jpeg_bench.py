@@ -1,7 +1,10 @@
 """The decode of one batch of 256 JPEG files of 500 x 375 (quality 90, 4:2:0) on the device (basd_amd.jpeg, three
 launches) beside Pillow's decode of the same files in 1 and in 16 processes on the same machine.
 usage: jpeg_bench.py [--batch 256] [--windows 5] [--per-window 10] [--processes 16] [--device-only]
-(--device-only: no worker processes and no Pillow timing, for a run under a profiler)
+                     [--entropy serial|parallel|both] [--sub-bytes N]
+(--device-only: no worker processes and no Pillow timing, for a run under a profiler; --entropy: the decoder's entropy
+stage, JpegDecoder(entropy=...); both: a serial and a parallel window in every round, one after the other, so the two
+are measured in the same run; --sub-bytes: JpegDecoder(sub_bytes=...) of the parallel stage, default its own)
 Where Pillow is importable the files are encoded with it (16 different pictures, repeated); otherwise the largest
 stream of tests/golden/jpeg_decode.npz is repeated and only the device is timed (the output says so).  The windows of
 the device and the Pillow runs alternate; the figures are medians over the windows."""
@@ -73,7 +76,10 @@ def main() -> None:
     ap.add_argument("--per-window", type=int, default=10)
     ap.add_argument("--processes", type=int, default=16)
     ap.add_argument("--device-only", action="store_true")
+    ap.add_argument("--entropy", choices=("serial", "parallel", "both"), default="serial")
+    ap.add_argument("--sub-bytes", type=int, default=None)
     args = ap.parse_args()
+    modes = ("serial", "parallel") if args.entropy == "both" else (args.entropy,)
     files, how = make_streams(args.batch)
     pillow = have_pillow()
     timed_pillow = pillow and not args.device_only
@@ -87,33 +93,41 @@ def main() -> None:
     pack_ms = (time.perf_counter() - t0) * 1e3
     assert packed.fallbacks == 0
     pinned = packed.pin_memory()
-    decoder = JpegDecoder(dev)
+    decoders = {m: JpegDecoder(dev, entropy=m, sub_bytes=args.sub_bytes if m == "parallel" else None) for m in modes}
     batch = pinned.to(dev, non_blocking=True)
-    for _ in range(3):
-        ragged = decoder(batch)
-    torch.cuda.synchronize()
-    assert decoder.status() == 0
     check = [0, args.batch // 2, args.batch - 1]
-    for i in check:
-        want = _pillow_pixels(files[i]) if pillow else decode_reference(files[i])
-        assert np.array_equal(ragged.image(i).cpu().numpy(), want), i
+    outputs = []
+    for decoder in decoders.values():
+        for _ in range(3):
+            ragged = decoder(batch)
+        torch.cuda.synchronize()
+        assert decoder.status() == 0
+        for i in check:
+            want = _pillow_pixels(files[i]) if pillow else decode_reference(files[i])
+            assert np.array_equal(ragged.image(i).cpu().numpy(), want), i
+        outputs.append(ragged.data)
+    assert all(torch.equal(outputs[0], other) for other in outputs[1:])       # every byte of the batch, mode against mode
+    del outputs
     stream_bytes = sum(len(f) for f in files)
     info = {"case": "the batch", "files": how, "batch": args.batch, "stream_bytes": stream_bytes,
             "decoded_bytes": packed.out_bytes, "workspace_bytes": packed.workspace_bytes,
-            "blocks_per_image": packed.max_blocks, "pack_jpegs_ms": round(pack_ms, 2)}
+            "blocks_per_image": packed.max_blocks, "pack_jpegs_ms": round(pack_ms, 2), "entropy": list(modes),
+            "sub_bytes": args.sub_bytes}
     print(json.dumps(info))
-    launches, calls, uploads, one, many = [], [], [], [], []
+    launches, calls = {m: [] for m in modes}, {m: [] for m in modes}
+    uploads, one, many = [], [], []
     for _ in range(args.windows):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        start.record()
-        for _ in range(args.per_window):
-            decoder(batch)
-        stop.record()
-        torch.cuda.synchronize()
-        calls.append((time.perf_counter() - t0) * 1e3 / args.per_window)
-        launches.append(start.elapsed_time(stop) / args.per_window)
+        for mode, decoder in decoders.items():
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            start.record()
+            for _ in range(args.per_window):
+                decoder(batch)
+            stop.record()
+            torch.cuda.synchronize()
+            calls[mode].append((time.perf_counter() - t0) * 1e3 / args.per_window)
+            launches[mode].append(start.elapsed_time(stop) / args.per_window)
         t0 = time.perf_counter()
         for _ in range(args.per_window):
             pinned.to(dev, non_blocking=True)
@@ -130,7 +144,7 @@ def main() -> None:
     if pool is not None:
         pool.close()
         pool.join()
-    assert decoder.status() == 0
+    assert all(decoder.status() == 0 for decoder in decoders.values())
 
     def line(case, ms):
         med = statistics.median(ms)
@@ -139,17 +153,25 @@ def main() -> None:
         print(json.dumps(row))
         return med
 
-    device_ms = line("device decode, three launches (device events)", launches)
-    line("JpegDecoder.__call__ (table copied, launched, waited for)", calls)
+    device = {m: line(f"device decode, {m} entropy stage, three launches (device events)", launches[m]) for m in modes}
+    for m in modes:
+        line(f"JpegDecoder.__call__, {m} (table copied, launched, waited for)", calls[m])
     line("upload of the packed files (pinned, one copy)", uploads)
+    device_ms = device[modes[-1]]
+    if len(modes) == 2:
+        gain = max(launches["parallel"]) < min(launches["serial"])
+        print(json.dumps({"case": "parallel against serial, same run", "serial_over_parallel":
+                          round(device["serial"] / device["parallel"], 2), "slowest_parallel_window_ms":
+                          round(max(launches["parallel"]), 3), "fastest_serial_window_ms":
+                          round(min(launches["serial"]), 3), "every_parallel_window_faster": gain}))
     if timed_pillow:
         one_ms = line("Pillow, 1 process", one)
         many_ms = line(f"Pillow, {args.processes} processes (results not sent back)", many)
-        print(f"\n  device {device_ms:.3f} ms per batch of {args.batch}; Pillow {one_ms:.1f} ms in 1 process, {many_ms:.1f} ms "
+        print(f"\n  device ({modes[-1]}) {device_ms:.3f} ms per batch of {args.batch}; Pillow {one_ms:.1f} ms in 1 process, {many_ms:.1f} ms "
               f"in {args.processes}: the device decode is faster by a factor of {one_ms / device_ms:.1f} and "
               f"{many_ms / device_ms:.1f}; images {check} compared byte for byte")
     else:
-        print(f"\n  device {device_ms:.3f} ms per batch of {args.batch}; Pillow not timed; images {check} compared "
+        print(f"\n  device ({modes[-1]}) {device_ms:.3f} ms per batch of {args.batch}; Pillow not timed; images {check} compared "
               f"with {'Pillow' if pillow else 'decode_reference'} byte for byte")
 
 

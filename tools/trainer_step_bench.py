@@ -8,8 +8,9 @@ fused: basd_amd.attention on each block's own qkv output, one launch per layer)
 normalised inside the fused launches)  [--trivial-augment]  (with --uint8: the flip and TrivialAugmentWide of the augmented
 batch on the device, basd_amd.trivial_augment, one launch per batch ahead of the mixer)
 [--resize-crop]  (with --uint8: the batch is a pinned RaggedBatch of 500 x 375 decoded images, uploaded inside the step;
-basd_amd.resize makes both views, one launch)  [--jpeg-decode]  (with --resize-crop: the batch is a pinned JpegBatch of
-the same pictures as JPEG files (tools/jpeg_bench.make_streams), decoded by basd_amd.jpeg ahead of the resize launch)"""
+basd_amd.resize makes both views, one launch)  [--jpeg-decode [serial|parallel]]  (with --resize-crop: the batch is a
+pinned JpegBatch of the same pictures as JPEG files (tools/jpeg_bench.make_streams), decoded by basd_amd.jpeg ahead of
+the resize launch; parallel: Trainer(jpeg_decode="parallel"), the entropy stage that decodes inside a segment)"""
 import argparse, os, sys, time
 from types import SimpleNamespace
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,7 +31,7 @@ ap.add_argument("--attn-capture", default="torch", choices=["torch", "fused"])
 ap.add_argument("--uint8", action="store_true")
 ap.add_argument("--trivial-augment", action="store_true")
 ap.add_argument("--resize-crop", action="store_true")
-ap.add_argument("--jpeg-decode", action="store_true")
+ap.add_argument("--jpeg-decode", nargs="?", const="serial", choices=("serial", "parallel"), default=None)
 args = ap.parse_args()
 if args.uint8 and args.mixup != "fused":
     ap.error("--uint8 needs --mixup fused")
@@ -63,7 +64,8 @@ tr = T.Trainer(student, cfg, teacher, student_info=SM.probe_model(student, 224),
                attn_capture=args.attn_capture,
                image_stats={"clean": ((0.5,) * 3, (0.25,) * 3), "augmented": ((0.5,) * 3, (0.25,) * 3)} if args.uint8 else None,
                mix_dtype=ac if args.uint8 else None, trivial_augment=args.trivial_augment,
-               resize_crop=args.resize_crop, jpeg_decode=args.jpeg_decode)
+               resize_crop=args.resize_crop,
+               jpeg_decode={None: False, "serial": True, "parallel": "parallel"}[args.jpeg_decode])
 g = torch.Generator().manual_seed(1)
 B = args.batch
 # images with per-image structure (a random colour cast + noise) so that the teacher features are not pure noise

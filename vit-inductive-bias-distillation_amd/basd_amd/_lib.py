@@ -125,6 +125,7 @@ SIGNATURES = {
     "basd_resize_crop": [vp, i64, vp, i32, i32, i32, i32, vp, vp, i32, vp],
     "basd_jpeg_status_bytes": [i32],
     "basd_jpeg_decode": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp],
+    "basd_jpeg_decode_parallel": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, i32, vp],
 }
 
 class ProcrustesArgs(C.Structure):

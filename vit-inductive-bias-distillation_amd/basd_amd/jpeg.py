@@ -1,7 +1,8 @@
 """The decode of the reference's loader -- ``Image.open(...).convert("RGB")`` in its workers -- on the device: the loader
 ships file bytes, ``collate_jpeg`` packs the streams of a batch into one uint8 buffer, that buffer is uploaded once, and
 three launches of ``basd_jpeg_decode`` (``csrc/jpeg.hip``) write the decoded images as the ``RaggedBatch`` of three
-channels ``ResizeCrop`` takes.
+channels ``ResizeCrop`` takes.  ``JpegDecoder(device, entropy="parallel")`` takes ``basd_jpeg_decode_parallel`` instead,
+whose first launch decodes inside a segment with a workgroup's lanes: the same bytes, opt-in.
 
 ``parse_jpeg`` reads a stream's header on the host and says whether the device decodes it (baseline, 8 bits, 1 or 3
 components, 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, YCbCr by libjpeg's rules: the scope is spelled out in
@@ -26,11 +27,13 @@ from ._launch import RecordTable, lives_on, raw_stream, require_gpu
 from .resize import RaggedBatch
 
 __all__ = ["JpegHeader", "parse_jpeg", "UnsupportedJpeg", "JpegBatch", "pack_jpegs", "collate_jpeg", "JpegDecoder",
-           "decode_reference", "pillow_fallback", "RECORD_DTYPE", "MAX_SIDE", "MAX_BATCH", "STATUS_NAMES"]
+           "decode_reference", "pillow_fallback", "RECORD_DTYPE", "MAX_SIDE", "MAX_BATCH", "STATUS_NAMES", "SUB_BYTES_MIN",
+           "SUB_BYTES_MAX"]
 
 MAX_SIDE = 16384                    # BASD_JPEG_MAX_SIDE
 MAX_BATCH = 65535                   # BASD_JPEG_MAX_BATCH
 KIND_STREAM, KIND_RAW = 0, 1        # BASD_JPEG_KIND_*
+SUB_BYTES_MIN, SUB_BYTES_MAX = 8, 1024   # BASD_JPEG_SUB_BYTES_*
 STATUS_NAMES = {0: "decoded", 1: "bad record", 2: "bad Huffman table", 3: "truncated", 4: "invalid Huffman code",
                 5: "missing or wrong restart marker", 6: "coefficient index past 63", 7: "DC value out of range"}
 
@@ -437,10 +440,30 @@ class JpegDecoder:
     launches on the current stream, no wait for the device.  ``workspace`` (coefficients and component planes, 192
     bytes per 8 x 8 block, behind the per-image status words) grows to the largest batch seen and is never cleared.
     ``status()`` reads the batch status word back (0: every image decoded; bit ``code - 1`` of ``STATUS_NAMES``
-    otherwise), ``image_status()`` the last batch's per-image words; both wait for the device."""
+    otherwise), ``image_status()`` the last batch's per-image words; both wait for the device.
 
-    def __init__(self, device) -> None:
+    ``entropy``: how the first launch decodes the Huffman data.  ``"serial"`` (the default, ``basd_jpeg_decode``): one
+    lane per entropy-coded segment, so a file without restart markers is decoded by one lane.  ``"parallel"``
+    (``basd_jpeg_decode_parallel``): a workgroup per image whose lanes decode sub-sequences of ``sub_bytes`` bytes of a
+    segment speculatively and synchronise (the scheme is in ``include/basd_hip.h``); ``sub_bytes``: ``None`` (the
+    built-in default) or a multiple of 8 in ``SUB_BYTES_MIN .. SUB_BYTES_MAX``.  Both give the same bytes and the same
+    status words for every stream, intact or damaged."""
+
+    ENTROPY = ("serial", "parallel")
+
+    def __init__(self, device, entropy: str = "serial", sub_bytes: Optional[int] = None) -> None:
+        if entropy not in self.ENTROPY:
+            raise ValueError(f"entropy must be one of {', '.join(repr(e) for e in self.ENTROPY)} (got {entropy!r})")
+        if sub_bytes is not None:
+            if entropy != "parallel":
+                raise ValueError('sub_bytes belongs to entropy="parallel" (the serial stage has no sub-sequences)')
+            if isinstance(sub_bytes, bool) or not isinstance(sub_bytes, int) or sub_bytes % 8 or \
+                    not SUB_BYTES_MIN <= sub_bytes <= SUB_BYTES_MAX:
+                raise ValueError(f"sub_bytes must be a multiple of 8 in {SUB_BYTES_MIN} .. {SUB_BYTES_MAX} "
+                                 f"(got {sub_bytes!r})")
         self.device = torch.device(device)
+        self.entropy = entropy
+        self.sub_bytes = sub_bytes
         self._records = RecordTable(RECORD_DTYPE)
         self.workspace: Optional[torch.Tensor] = None
         self.used_bytes = 0
@@ -479,9 +502,13 @@ class JpegDecoder:
             self.workspace = torch.empty(need, dtype=torch.uint8, device=batch.device)
         self.used_bytes = need
         self._records.stage(B, batch.device)[...] = rec
-        _lib.call("basd_jpeg_decode", batch.data.data_ptr(), batch.data.numel(), out.data_ptr(), out.numel(), B,
-                  self._records.upload(), self.workspace.data_ptr(), self.workspace.numel(), self._records.status_ptr,
-                  batch.max_blocks, batch.max_pixels, raw_stream(batch.device.index))
+        args = (batch.data.data_ptr(), batch.data.numel(), out.data_ptr(), out.numel(), B, self._records.upload(),
+                self.workspace.data_ptr(), self.workspace.numel(), self._records.status_ptr, batch.max_blocks,
+                batch.max_pixels)
+        if self.entropy == "parallel":
+            _lib.call("basd_jpeg_decode_parallel", *args, self.sub_bytes or 0, raw_stream(batch.device.index))
+        else:
+            _lib.call("basd_jpeg_decode", *args, raw_stream(batch.device.index))
         return ragged
 
 

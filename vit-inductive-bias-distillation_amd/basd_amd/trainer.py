@@ -105,12 +105,14 @@ class Trainer:
     batch's optional ``"crop_params"`` entry (a ``CropParams``).  ``prepare_views(batch)`` returns the two batches.
     ``jpeg_decode``: ``True`` (it needs ``resize_crop``) lets the batch's ``"images"`` be a ``JpegBatch`` of the files' bytes
     (the loader does not decode, ``collate_fn=collate_jpeg``): three launches of ``basd_amd.jpeg.JpegDecoder`` decode it
-    into the ``RaggedBatch`` the resize launch takes; a ``RaggedBatch`` is taken as before."""
+    into the ``RaggedBatch`` the resize launch takes; a ``RaggedBatch`` is taken as before.  ``"parallel"`` is ``True`` with
+    ``JpegDecoder(entropy="parallel")``: the entropy stage decodes inside a segment with a workgroup's lanes instead of
+    one lane per segment (the same bytes; what it gains is in DESIGN.md section 8).  ``False``: no decoder."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
-                 resize_crop: bool = False, jpeg_decode: bool = False) -> None:
+                 resize_crop: bool = False, jpeg_decode=False) -> None:
         self.config = config
         self.device = next(student_model.parameters()).device
         self.criterion = nn.CrossEntropyLoss(label_smoothing=config.training.label_smoothing)
@@ -169,12 +171,14 @@ class Trainer:
             from .resize import ResizeCrop
             self._resizer = ResizeCrop(config.model.vit.img_size, config.data.eval_crop_ratio, device=self.device)
         self._decoder = None
+        if not (isinstance(jpeg_decode, bool) or jpeg_decode == "parallel"):
+            raise ValueError(f"jpeg_decode must be True, False or 'parallel', not {jpeg_decode!r}")
         if jpeg_decode:
             if not resize_crop:
                 raise ValueError("jpeg_decode needs resize_crop=True (the decoded images are a ragged batch, which the "
                                  "resize launch takes); got resize_crop=False")
             from .jpeg import JpegDecoder
-            self._decoder = JpegDecoder(self.device)
+            self._decoder = JpegDecoder(self.device, entropy="parallel" if jpeg_decode == "parallel" else "serial")
         self.best_val_acc = 0.0
         self.metrics_history = defaultdict(list)
         self._params = [p for p in student_model.parameters() if p.requires_grad]

@@ -292,6 +292,180 @@ BASD_HD bool jpeg_segments_ok(const BasdJpegRecord& r, const JpegGeometry& g) {
     return (long)r.n_seg == want;
 }
 
+// ---- decoding inside a segment in parallel (basd_jpeg_decode_parallel) -----------------------------------------------
+// A segment's bytes are cut into sub-sequences of `sub_bytes`; one lane decodes one sub-sequence, first from a guessed
+// state, then again from the state its predecessor handed over, until nothing changes (csrc/jpeg.hip holds the rounds,
+// the barriers and the prefix sums; tools/jpeg_parallel_host_check.cpp runs the same functions as loops).  What is
+// handed over is CANONICAL: it names a bit of the stream, not a state of the reader, so two decoders that stand at the
+// same bit hand over equal states whatever their refills were.
+//   pos    offset in the stream of the first byte of which no bit has been taken (a stuffed 00 counts to its FF);
+//   rest   k | j << 6 | rem << 9 | bits << 12: the zigzag index of the next coefficient (0: a block begins), the slot of
+//          the block in its MCU, how many bits of the data byte ahead of `pos` are still to be taken, and those bits
+//          (so a decoder that resumes never looks behind `pos`); -1: no state (a bad code, or the data ran out).
+struct JpegSubState {
+    int pos, rest;
+};
+constexpr int kJpegSubNone = -1;
+constexpr int kJpegSubOpenEnd = 0x7fffffff;              // `sub_end` of a segment's last sub-sequence: it has no end
+
+BASD_HD bool jpeg_sub_same(const JpegSubState& a, const JpegSubState& b) { return a.pos == b.pos && a.rest == b.rest; }
+
+// What one pass of a lane over its sub-sequence gives.
+struct JpegSubPass {
+    JpegSubState exit;
+    int blocks;                        // blocks that BEGAN in the sub-sequence
+    unsigned dc[3];                    // count pass: per component the sum of the DC differences met (modulo 2^32: a
+                                       // true prefix of them is a predictor and fits 16 bits); write pass: unused
+    int error;                         // write pass: 0 or the BASD_JPEG_BAD_* code the serial decoder meets here
+};
+
+// One segment's constants for the passes.
+struct JpegSubSegment {
+    const unsigned char* src;          // the byte buffer
+    long stream_at;                    // r.src_offset
+    int end;                           // offset in the stream at which the segment's data ends
+    int bpm, luma;                     // blocks per MCU; slot of the Cb block (slots below it are luma)
+    const JpegHuff* tables;
+};
+
+// The range of segment `seg`, the checks of jpeg_decode_segment: 0 or BASD_JPEG_BAD_RESTART.
+BASD_HD int jpeg_segment_range(const BasdJpegRecord& r, const JpegGeometry& g, const unsigned char* src, int seg,
+                               int& start, int& end, long& first, long& last) {
+    const unsigned char* stream = src + r.src_offset;
+    end = r.src_len + 2;
+    __builtin_memcpy(&start, __builtin_assume_aligned(src + r.seg_offset + 4L * seg, 4), 4);
+    if (seg + 1 < r.n_seg) __builtin_memcpy(&end, __builtin_assume_aligned(src + r.seg_offset + 4L * (seg + 1), 4), 4);
+    if (end < 2) return BASD_JPEG_BAD_RESTART;
+    end -= 2;
+    if (start < 2 || start > r.src_len || end < start || end > r.src_len) return BASD_JPEG_BAD_RESTART;
+    if (seg > 0 && (stream[start - 2] != 0xFF || stream[start - 1] != 0xD0 + ((seg - 1) & 7)))
+        return BASD_JPEG_BAD_RESTART;
+    const long per = r.restart > 0 ? r.restart : g.mcus;
+    first = (long)seg * per;
+    last = first + per < g.mcus ? first + per : g.mcus;
+    return 0;
+}
+
+// A reader that resumes at the bit `s` names; `bias`: what to add to b.pos to get an offset in the stream.
+BASD_HD void jpeg_sub_open(JpegBits& b, int& bias, const JpegSubSegment& g, const JpegSubState& s) {
+    jpeg_bits_open(b, g.src, g.stream_at + s.pos, g.end - s.pos);
+    bias = s.pos - b.pos;
+    const int rem = (s.rest >> 9) & 7;
+    if (rem) {
+        b.acc = (uint64_t)((s.rest >> 12) & 127) << (64 - rem);
+        b.nbits = rem;
+    }
+}
+
+// The bit the reader stands at (b.nbits >= 0), as the `pos`, `rem` and `bits` of a JpegSubState.  Whole bytes that
+// wait in `acc` are pushed back: each is one byte of the stream, or two where it is FF (its stuffed 00).  `opened`:
+// b.pos at jpeg_sub_open.  Once the data has ended on an FF that is not followed by 00, b.pos stands behind that FF.
+BASD_HD void jpeg_sub_tell(const JpegBits& b, int bias, int opened, int& pos, int& rem, int& bits) {
+    int fed = b.pos;
+    if (!b.more && fed > opened && b.base[fed - 1] == 0xFF) --fed;     // an FF that was taken is followed by its 00
+    rem = b.nbits & 7;
+    bits = rem ? (int)(b.acc >> (64 - rem)) : 0;
+    const uint64_t whole = ~(b.acc << rem);                            // the waiting bytes, inverted (behind them: FF)
+    const uint64_t low = 0x7f7f7f7f7f7f7f7fULL;
+    const uint64_t not_ff = (((whole & low) + low) | whole) & ~low;     // bit 7 of every byte that was not FF
+    pos = fed + bias - (b.nbits >> 3) - (8 - __builtin_popcountll(not_ff));
+}
+
+// Has a segment of `nblocks` blocks been decoded to its end, given the blocks begun up to a chunk's end and the state
+// handed over there by passes that do not know the block count?  More blocks begun: the last one ended (what follows
+// is padding read as a block).  Exactly `nblocks` begun: it ended if the next symbol is a DC symbol (index 0), or if
+// there is no state -- the last block itself was decoded without an error by the write pass (the caller has seen to
+// that), so what failed is the symbol behind it.  Else the block runs on into the next chunk.
+BASD_HD bool jpeg_sub_complete(unsigned begun, long nblocks, int rest) {
+    if ((long)begun != nblocks) return (long)begun > nblocks;
+    return rest == kJpegSubNone || (rest & 63) == 0;
+}
+
+BASD_HD int jpeg_sub_rest(int j, int k, int rem, int bits) { return k | (j << 6) | (rem << 9) | (bits << 12); }
+
+// One pass of a lane: from state `in` up to the first symbol that begins at or behind `sub_end` (a symbol of whose first
+// byte bits are left begins in that byte; kJpegSubOpenEnd: no end).  kWrite false (speculation and synchronisation):
+// nothing is written, `blocks` and `dc` are counted, and whatever goes wrong only makes the exit state kJpegSubNone.
+// kWrite true: `in` is the true state; block `block_at` (index in the segment) is the first that begins here, `pred`
+// the predictors ahead of it; coefficients are stored one by one into the zeroed area `coef` (the segment's), a block
+// at or past `block_end` is never begun, and an error is the serial decoder's.
+template <bool kWrite>
+BASD_HD JpegSubPass jpeg_sub_pass(const JpegSubSegment& g, JpegSubState in, int sub_end, short* coef, long block_at,
+                                  long block_end, int pred0, int pred1, int pred2) {
+    JpegSubPass out = {};
+    out.exit.pos = 0;
+    out.exit.rest = kJpegSubNone;
+    if (in.rest == kJpegSubNone) return out;
+    int j = (in.rest >> 6) & 7, k = in.rest & 63;
+    short* to = coef;                                                  // the block under way (write pass)
+    if (kWrite) {
+        if ((k ? block_at - 1 : block_at) >= block_end) return out;   // the segment's blocks ended ahead of this lane
+        if (k && block_at < 1) return out;                             // (a true state inside a block follows its beginning)
+        to = coef + (block_at - 1) * 64;                               // looked at only where k > 0
+    }
+    JpegBits b;
+    int bias;
+    jpeg_sub_open(b, bias, g, in);
+    const int opened = b.pos;
+    int bad = 0;
+    for (;;) {
+        jpeg_bits_fill(b);
+        if (b.pos + bias >= sub_end) {                                 // else the bytes fed, and so the bit ahead, lie before it
+            int pos, rem, bits;
+            jpeg_sub_tell(b, bias, opened, pos, rem, bits);
+            if (pos - (rem ? 1 : 0) >= sub_end) {
+                out.exit.pos = pos;
+                out.exit.rest = jpeg_sub_rest(j, k, rem, bits);
+                return out;
+            }
+        }
+        const int c = j < g.luma ? 0 : j == g.luma ? 1 : 2;
+        if (k == 0) {
+            if (kWrite && block_at + out.blocks >= block_end) return out;     // the segment is complete: padding follows
+            int s = jpeg_symbol(b, g.tables + c);
+            if (b.nbits < 0) { bad = BASD_JPEG_TRUNCATED; break; }
+            if (s < 0) { bad = -s; break; }
+            if (s > 15) { bad = BASD_JPEG_BAD_CODE; break; }
+            const int diff = s ? jpeg_extend(b, s) : 0;
+            if (b.nbits < 0) { bad = BASD_JPEG_TRUNCATED; break; }
+            if (kWrite) {
+                int& pred = c == 0 ? pred0 : c == 1 ? pred1 : pred2;
+                pred += diff;
+                if (pred < -32768 || pred > 32767) { bad = BASD_JPEG_BAD_VALUE; break; }
+                to = coef + (block_at + out.blocks) * 64;
+                to[0] = (short)pred;
+            } else {
+                out.dc[c] += (unsigned)diff;
+            }
+            ++out.blocks;
+            k = 1;
+            continue;
+        }
+        const int rs = jpeg_symbol(b, g.tables + 3 + c);
+        if (b.nbits < 0) { bad = BASD_JPEG_TRUNCATED; break; }
+        if (rs < 0) { bad = -rs; break; }
+        const int s = rs & 15;
+        if (s) {
+            k += rs >> 4;
+            if (k > 63) { bad = BASD_JPEG_BAD_INDEX; break; }
+            const int v = jpeg_extend(b, s);
+            if (b.nbits < 0) { bad = BASD_JPEG_TRUNCATED; break; }
+            if (kWrite) to[k] = (short)v;
+            ++k;
+        } else if ((rs >> 4) == 15) {
+            k += 16;
+        } else {
+            k = 64;
+        }
+        if (k > 63) {                                                  // the block is complete
+            k = 0;
+            j = j + 1 == g.bpm ? 0 : j + 1;
+        }
+    }
+    if (kWrite) out.error = bad;
+    return out;
+}
+
 // ---- IDCT ---------------------------------------------------------------------------------------------------------
 BASD_HD void jpeg_idct_1d(const int64_t c[8], int64_t out[8]) {
     int64_t z1 = (c[2] + c[6]) * 4433;
