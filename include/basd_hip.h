@@ -683,7 +683,59 @@ int basd_sfadamw_step(const BasdSfAdamwTensor* table, const int* chunks, int n_c
 int basd_sfadamw_swap(const BasdSfAdamwTensor* table, const int* chunks, int n_chunks, const float* weights,
                       int n_groups, hipStream_t stream);
 
-/* diagnostics: kernel launches made by the two entry points above since the library was loaded (process-wide). */
+/* What the clipped step decided, on the DEVICE (32 bytes, 8-byte aligned; zero it once).  norm_sq: the fp64 sum of
+ * the squared raw gradients; norm = |grad_scale| sqrt(norm_sq): the 2-norm of the gradients as the update saw them;
+ * (fp32: it reads inf past 3.4e38 while norm_sq, which the guard looks at, is still finite); coef: the clipping
+ * coefficient that was applied; skipped: 1 if this step left y, z, v alone; skipped_total: the number of such steps
+ * since the struct was zeroed. */
+typedef struct BasdGradVerdict {
+    double norm_sq;
+    float norm;
+    float coef;
+    int skipped;
+    int skipped_total;
+    int pad[2];
+} BasdGradVerdict;
+
+/* Number of partial sums basd_grad_sqnorm writes for a chunk list of n_chunks entries: a pure function of n_chunks,
+ * 1 <= value <= 1024.  It is the grid of the norm pass and thereby fixes the order of summation. */
+int basd_grad_sqnorm_parts(int n_chunks);
+
+/* replaces: the norm half of `torch.nn.utils.clip_grad_norm_` (the reference's trainer does not clip; a trainer on
+ * `accelerate` would call `accelerator.clip_grad_norm_`) over the gradients of ALL tensors of the table, as n_partials
+ * fp64 partial sums of squares.  Same table and chunk list as
+ * basd_sfadamw_step; rows with grad == NULL are skipped.  n_partials (= basd_grad_sqnorm_parts(n_chunks)) workgroups
+ * walk the chunk list with a grid stride; every lane squares its fp32 elements in fp64 (exact) and accumulates them
+ * in fp64; lanes are combined in a fixed order (butterfly inside a wave, the waves in index order through LDS) and
+ * workgroup b stores partials[b].  The same gradients give the same bits on every call.  16-byte loads where the
+ * gradient pointer allows them, 4-byte loads for a misaligned gradient and the last numel % 4 elements.  No workgroup
+ * reads what another wrote: the partials are summed by the kernel that consumes them (basd_sfadamw_step_clipped).
+ * partials: n_partials doubles on the device, 8-byte aligned, all overwritten.  ONE launch; n_chunks == 0 launches
+ * nothing. */
+int basd_grad_sqnorm(const BasdSfAdamwTensor* table, const int* chunks, int n_chunks, double* partials, int n_partials,
+                     hipStream_t stream);
+
+/* replaces: `clip_grad_norm_(params, max_norm)` + a non-finite guard + `optimizer.step()` + `optimizer.zero_grad()`.
+ * basd_sfadamw_step behind a prologue: every workgroup sums the n_partials partials of basd_grad_sqnorm in one fixed
+ * order (the same in every workgroup) and forms in fp64
+ *   norm_sq = sum partials;  norm = |grad_scale| sqrt(norm_sq);
+ *   coef = max_norm > 0 and max_norm / (norm + 1e-6) < 1 ? max_norm / (norm + 1e-6) : 1, rounded once to fp32
+ *          (the `clip_grad_norm_` formula; a NaN norm clips nothing);
+ *   skip = skip_nonfinite and norm_sq is not finite (one inf or NaN gradient element makes it so; finite fp32
+ *          gradients cannot: 2^25 elements of 3.4e38^2 are far inside fp64).
+ * Not skipped: the recurrence of basd_sfadamw_step with g = grad * fl32(grad_scale * coef) -- with coef == 1 the bytes
+ * of y, z, v and grad are those of basd_sfadamw_step with grad_scale, else those with fl32(grad_scale * coef).
+ * Skipped: y, z and v are not written; the gradients are still zeroed if zero_grad.
+ * Lane 0 of workgroup 0 writes *verdict (skipped_total by a plain read-modify-write: launches are stream-ordered).
+ * partials, verdict: on the device, non-null, 8-byte aligned; n_partials == basd_grad_sqnorm_parts(n_chunks).
+ * max_norm <= 0 = no clipping.  ONE launch; n_chunks == 0 launches nothing (and leaves *verdict alone). */
+int basd_sfadamw_step_clipped(const BasdSfAdamwTensor* table, const int* chunks, int n_chunks,
+                              const BasdSfAdamwGroup* groups, int n_groups, float grad_scale, int zero_grad,
+                              const double* partials, int n_partials, double max_norm, int skip_nonfinite,
+                              BasdGradVerdict* verdict, hipStream_t stream);
+
+/* diagnostics: kernel launches made by the entry points above (step, swap, norm pass, clipped step) since the
+ * library was loaded (process-wide). */
 long basd_sfadamw_launches(void);
 
 /* ---- validation: loss, top-1 and top-k of one batch in one launch ------------------------------------ */

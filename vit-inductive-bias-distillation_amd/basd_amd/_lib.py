@@ -115,6 +115,9 @@ SIGNATURES = {
     "basd_sfadamw_chunk": [],
     "basd_sfadamw_step": [vp, vp, i32, vp, i32, f32, i32, vp],
     "basd_sfadamw_swap": [vp, vp, i32, vp, i32, vp],
+    "basd_grad_sqnorm_parts": [i32],
+    "basd_grad_sqnorm": [vp, vp, i32, vp, i32, vp],
+    "basd_sfadamw_step_clipped": [vp, vp, i32, vp, i32, f32, i32, vp, i32, f64, i32, vp, vp],
     "basd_sfadamw_launches": [],
     "basd_eval_batch": [vp, i32, i64, i32, i32, vp, i32, vp, f32, i32, vp, vp],
     "basd_mix_batch": [vp, i32, vp, i32, i32, i32, i32, i32, i32, f64, i32, i32, i32, i32, vp, vp, vp, i32, f64, vp,

@@ -10,7 +10,10 @@ The update of ALL tensors of ALL parameter groups is ONE launch of ``basd_sfadam
 * the per-group scalars of a step (``schedule``: plain Python, no GPU) travel in the kernel arguments, so a steady-state
   ``step()`` issues no host-to-device copy and never waits for the device;
 * ``zero_grad_in_step=True`` clears the gradients in the same pass (use it with gradients that stay in place, such as
-  ``ddp.FlatGradBucket`` views), ``grad_scale`` folds a ``1 / world`` into it.
+  ``ddp.FlatGradBucket`` views), ``grad_scale`` folds a ``1 / world`` into it;
+* opt-in, ``max_grad_norm`` / ``skip_nonfinite``: global-norm clipping and a guard against inf / NaN gradients, decided
+  on the device.  ``step()`` is then TWO launches (``basd_grad_sqnorm``: fp64 partial sums of squares;
+  ``basd_sfadamw_step_clipped``: the same update behind a prologue that sums them), still without a copy or a wait.
 
 fp32 parameters, state and gradients only; dense contiguous tensors on ONE device.  There is no CPU fallback.
 
@@ -20,6 +23,7 @@ published source, and fidelity to an installed ``schedulefree`` (the ``state_dic
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -30,6 +34,17 @@ __all__ = ["AdamWScheduleFree", "schedule", "MAX_GROUPS"]
 
 MAX_GROUPS = 8          # BASD_SFADAMW_MAX_GROUPS of include/basd_hip.h
 _ALIGN = 4              # elements: every state segment starts on a 16-byte boundary
+_UNSET = object()       # step(max_grad_norm=...): "as the optimizer was built" (None means: no clipping in this call)
+
+
+def _checked_max_norm(value):
+    """``None`` (no clipping) or a finite number > 0 as a float; anything else is a ``ValueError``."""
+    if value is None:
+        return None
+    norm = float(value)
+    if not (math.isfinite(norm) and norm > 0.0):
+        raise ValueError(f"max_grad_norm must be None or a finite number greater than 0, not {value!r}")
+    return norm
 
 
 class _GroupScalars(C.Structure):
@@ -60,15 +75,30 @@ class AdamWScheduleFree(torch.optim.Optimizer):
 
     As in the package, a fresh optimizer is in eval mode: call ``.train()`` before the first ``step()`` and ``.eval()``
     before validation or a checkpoint; ``step()`` in eval mode raises.  Keyword-only additions: ``zero_grad_in_step``
-    and ``grad_scale``, both overridable per call (``step(grad_scale=..., zero_grad_in_step=...)``)."""
+    and ``grad_scale``, both overridable per call (``step(grad_scale=..., zero_grad_in_step=...)``).
+
+    Keyword-only as well, and overridable per call: ``max_grad_norm`` (``None`` or a finite number > 0) and
+    ``skip_nonfinite``.  The package has neither, so they are attributes of the optimizer and not entries of the
+    parameter groups: the ``state_dict`` is unchanged.  ``max_grad_norm``: the gradients of ALL groups together, times ``grad_scale``, are
+    scaled by ``min(1, max_grad_norm / (norm + 1e-6))`` as by ``torch.nn.utils.clip_grad_norm_`` -- inside the update:
+    the stored gradients are not rewritten.  ``skip_nonfinite``: a step whose gradients hold an inf or a NaN leaves
+    the parameters, ``z`` and ``exp_avg_sq`` untouched (the gradients are still zeroed with ``zero_grad_in_step``).
+    The host cannot know of a skipped step without waiting for the device, so ``k``, ``weight_sum`` and ``lr_max``
+    advance as for any step and only the device state stands still (``torch.amp.GradScaler`` does wait, and does not
+    count a skipped step).  ``last_grad_norm()``, ``last_clip_coef()`` and ``last_step_skipped()`` return 0-dim device
+    tensors without waiting; ``skipped_steps()`` returns an ``int`` and is the one call that waits."""
 
     def __init__(self, params, lr=0.0025, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, warmup_steps=0, r=0.0,
-                 weight_lr_power=2.0, foreach=True, *, zero_grad_in_step: bool = False, grad_scale: float = 1.0):
+                 weight_lr_power=2.0, foreach=True, *, zero_grad_in_step: bool = False, grad_scale: float = 1.0,
+                 max_grad_norm: float | None = None, skip_nonfinite: bool = False):
         defaults = dict(lr=lr, betas=betas, eps=eps, r=r, k=0, warmup_steps=warmup_steps, train_mode=False,
                         weight_sum=0.0, lr_max=-1.0, scheduled_lr=0.0, weight_lr_power=weight_lr_power,
                         weight_decay=weight_decay, foreach=foreach)
         self.zero_grad_in_step = bool(zero_grad_in_step)
         self.grad_scale = float(grad_scale)
+        self.max_grad_norm = _checked_max_norm(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._partials = self._verdict = None   # the norm pass's fp64 partial sums; BasdGradVerdict as 4 x 8 bytes
         self.table_uploads = 0          # how often the device table was (re)written: 1 in the steady state
         self._zbuf = self._vbuf = None  # the flat state buffers; None = state not built (or stale)
         self._params: list = []
@@ -177,14 +207,23 @@ class AdamWScheduleFree(torch.optim.Optimizer):
             host = torch.tensor(pairs if pairs else [[0, 0]], dtype=torch.int32).pin_memory()
             self._chunks = torch.empty(host.shape, dtype=torch.int32, device=device)
             self._chunks.copy_(host, non_blocking=True)
+            self._partials = torch.zeros(_lib.query("basd_grad_sqnorm_parts", self._n_chunks), dtype=torch.float64,
+                                         device=device)
+            if self._verdict is None:       # kept over a new layout: ``skipped_total`` counts for the optimizer's life
+                self._verdict = torch.zeros(4, dtype=torch.float64, device=device)
         self._table = self._upload(rows, device)
         self._signature = signature
         self.table_uploads += 1
 
     # ---- the public interface ----------------------------------------------------------------------------------
-    def step(self, closure=None, *, grad_scale: float | None = None, zero_grad_in_step: bool | None = None):
+    def step(self, closure=None, *, grad_scale: float | None = None, zero_grad_in_step: bool | None = None,
+             max_grad_norm=_UNSET, skip_nonfinite: bool | None = None):
         """One update of every parameter that has a gradient (a parameter whose ``.grad`` is ``None`` is skipped; its
-        group's ``k`` still advances).  One kernel launch, queued on the current stream."""
+        group's ``k`` still advances).  One kernel launch, queued on the current stream; two with ``max_grad_norm`` or
+        ``skip_nonfinite`` (for this call: ``max_grad_norm=None`` switches the clipping off, leaving the argument out
+        keeps the optimizer's setting).  A step the guard skips on the device still advances ``k``."""
+        max_norm = self.max_grad_norm if max_grad_norm is _UNSET else _checked_max_norm(max_grad_norm)
+        guard = self.skip_nonfinite if skip_nonfinite is None else bool(skip_nonfinite)
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -200,11 +239,43 @@ class AdamWScheduleFree(torch.optim.Optimizer):
             s.lr, s.ckp1, s.bias_correction2 = now["lr"], now["ckp1"], now["bias_correction2"]
             s.beta1, s.beta2 = group["betas"]
             s.eps, s.weight_decay = group["eps"], group["weight_decay"]
-        _lib.call("basd_sfadamw_step", self._table.data_ptr(), self._chunks.data_ptr(), self._n_chunks,
-                  C.addressof(scalars), len(self.param_groups),
-                  self.grad_scale if grad_scale is None else float(grad_scale),
-                  int(self.zero_grad_in_step if zero_grad_in_step is None else zero_grad_in_step), _stream())
+        scale = self.grad_scale if grad_scale is None else float(grad_scale)
+        zero = int(self.zero_grad_in_step if zero_grad_in_step is None else zero_grad_in_step)
+        table, chunks, stream = self._table.data_ptr(), self._chunks.data_ptr(), _stream()
+        if max_norm is None and not guard:
+            _lib.call("basd_sfadamw_step", table, chunks, self._n_chunks, C.addressof(scalars), len(self.param_groups),
+                      scale, zero, stream)
+            return loss
+        parts = self._partials
+        _lib.call("basd_grad_sqnorm", table, chunks, self._n_chunks, parts.data_ptr(), parts.numel(), stream)
+        _lib.call("basd_sfadamw_step_clipped", table, chunks, self._n_chunks, C.addressof(scalars),
+                  len(self.param_groups), scale, zero, parts.data_ptr(), parts.numel(),
+                  0.0 if max_norm is None else max_norm, int(guard), self._verdict.data_ptr(), stream)
         return loss
+
+    # ---- what the last clipped / guarded step decided (BasdGradVerdict of include/basd_hip.h) ---------------------
+    def _verdict_field(self, dtype, index: int) -> torch.Tensor:
+        if self._verdict is None:
+            raise RuntimeError("no step has run yet: there is no verdict to read")
+        return self._verdict.view(dtype)[index].clone()
+
+    def last_grad_norm(self) -> torch.Tensor:
+        """The 2-norm of all gradients of the last step made with ``max_grad_norm`` or ``skip_nonfinite``, as the
+        update saw them (times ``grad_scale``, before clipping): a 0-dim fp32 device tensor, a copy.  Does not wait."""
+        return self._verdict_field(torch.float32, 2)
+
+    def last_clip_coef(self) -> torch.Tensor:
+        """The coefficient that step multiplied the gradients by (1 = not clipped): 0-dim fp32, a copy, no wait."""
+        return self._verdict_field(torch.float32, 3)
+
+    def last_step_skipped(self) -> torch.Tensor:
+        """1 if the guard skipped that step, else 0: 0-dim int32, a copy, no wait."""
+        return self._verdict_field(torch.int32, 4)
+
+    def skipped_steps(self) -> int:
+        """How many steps the guard has skipped over this optimizer's life.  The one call here that WAITS for the
+        device: call it at an epoch's end."""
+        return 0 if self._verdict is None else int(self._verdict.view(torch.int32)[5].item())
 
     def _swap(self, to_train: bool) -> None:
         if self.param_groups[0]["train_mode"] == to_train:

@@ -107,12 +107,25 @@ class Trainer:
     (the loader does not decode, ``collate_fn=collate_jpeg``): three launches of ``basd_amd.jpeg.JpegDecoder`` decode it
     into the ``RaggedBatch`` the resize launch takes; a ``RaggedBatch`` is taken as before.  ``"parallel"`` is ``True`` with
     ``JpegDecoder(entropy="parallel")``: the entropy stage decodes inside a segment with a workgroup's lanes instead of
-    one lane per segment (the same bytes; what it gains is in DESIGN.md section 8).  ``False``: no decoder."""
+    one lane per segment (the same bytes; what it gains is in DESIGN.md section 8).  ``False``: no decoder.
+    ``max_grad_norm`` (``None`` or a finite number > 0) and ``skip_nonfinite``: global-norm clipping and the guard against
+    inf / NaN gradients of ``AdamWScheduleFree``, decided on the device inside the optimizer's two launches (they need
+    ``optimizer="schedulefree"``).  The norm is taken over the student's and the loss's gradients together, after the
+    all-reduce and with the ``grad_scale`` the update gets, so every rank forms the same coefficient and the same verdict.
+    With either, ``train_step`` also returns ``"grad_norm"`` and ``_train_epoch`` ``"grad_norm"`` (the mean over the steps
+    that were not skipped, accumulated on the device) and ``"skipped_steps"`` (this epoch's count, one read at its end).
+    A skipped step still advances the optimizer's ``k`` (see ``AdamWScheduleFree``)."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
-                 resize_crop: bool = False, jpeg_decode=False) -> None:
+                 resize_crop: bool = False, jpeg_decode=False, max_grad_norm=None,
+                 skip_nonfinite: bool = False) -> None:
+        self._guarded = max_grad_norm is not None or bool(skip_nonfinite)
+        self._skipped_seen = 0
+        if self._guarded and optimizer != "schedulefree":
+            raise ValueError("max_grad_norm and skip_nonfinite are part of AdamWScheduleFree's update: they need "
+                             f"optimizer='schedulefree'; got optimizer={optimizer!r}")
         self.config = config
         self.device = next(student_model.parameters()).device
         self.criterion = nn.CrossEntropyLoss(label_smoothing=config.training.label_smoothing)
@@ -133,7 +146,8 @@ class Trainer:
         elif optimizer == "schedulefree":
             from .optim import AdamWScheduleFree
             self.optimizer = AdamWScheduleFree(student_model.parameters(), lr=config.training.learning_rate,
-                                               weight_decay=config.training.weight_decay)
+                                               weight_decay=config.training.weight_decay,
+                                               max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         else:
             raise ValueError(f"optimizer must be 'adamw' or 'schedulefree', not {optimizer!r}")
         self.optimizer.add_param_group({"params": list(self.basd_loss.parameters())})
@@ -263,7 +277,10 @@ class Trainer:
             self._all_reduce_gradients()
             self.optimizer.step()
             self.optimizer.zero_grad(set_to_none=False)
-        return {"loss": loss.detach(), "correct": logits.detach().argmax(1).eq(targets).sum(), "n": targets.size(0)}
+        out = {"loss": loss.detach(), "correct": logits.detach().argmax(1).eq(targets).sum(), "n": targets.size(0)}
+        if self._guarded:
+            out["grad_norm"] = self.optimizer.last_grad_norm()
+        return out
 
     def _optimizer_mode(self, train: bool) -> bool:
         """``optimizer.train()`` / ``optimizer.eval()`` where the optimizer has them (reference trainer.py:180,184);
@@ -296,6 +313,9 @@ class Trainer:
         total_loss = torch.zeros((), device=self.device)
         correct = torch.zeros((), device=self.device, dtype=torch.long)
         total = 0
+        if self._guarded:
+            norm_sum = torch.zeros((), device=self.device)
+            norm_steps = torch.zeros((), device=self.device)
         self.model.train()
         self._optimizer_mode(True)
         for batch in train_loader:
@@ -303,8 +323,17 @@ class Trainer:
             total_loss += out["loss"] * out["n"]
             correct += out["correct"]
             total += out["n"]
+            if self._guarded:
+                kept = self.optimizer.last_step_skipped() == 0
+                norm_sum += torch.where(kept, out["grad_norm"], 0.0)
+                norm_steps += kept
         self._finish_loss()
-        return {"train_loss": (total_loss / total).item(), "train_acc": 100.0 * (correct / total).item()}
+        metrics = {"train_loss": (total_loss / total).item(), "train_acc": 100.0 * (correct / total).item()}
+        if self._guarded:
+            skipped = self.optimizer.skipped_steps()                # the epoch's one read of the verdict
+            metrics["grad_norm"] = (norm_sum / norm_steps).item()  # NaN when every step was skipped
+            metrics["skipped_steps"], self._skipped_seen = skipped - self._skipped_seen, skipped
+        return metrics
 
     def _finish_loss(self) -> None:
         """Complete what the loss may have deferred past its last call (a rank read-back in ``sync_ranks = False`` mode,
