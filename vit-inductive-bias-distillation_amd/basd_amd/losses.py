@@ -646,7 +646,16 @@ class GrassmannianLayerSelector(nn.Module):
                 xs = ops._check_common_layout([ops.as_supported(x) for x in students], "student token tensors")
                 s_stack, means = ops.centered_grams(xs)
                 st["means"] = means
-                if stud_jacobi:
+                if stud_jacobi and all_student_vectors:
+                    # The backward needs ALL eigenvectors.  A normalised column of G J is vector i only to about
+                    # eps lam_0 / lam_i: for a Gram with a block at 2^-24 of the rest the 32 vectors of that block came
+                    # out with |V V^T - I| = 0.66 and the student gradient 146 % off.  So the solver runs on [G ; I] and
+                    # the vectors are the columns of J itself: orthonormal to round-off whatever the spectrum, and
+                    # J diag(lam) J^T is G to eps lam_0, which is all that V K2 V^T asks of them.
+                    full = ops._device_consts((d_s,) * E, torch.int32, s_stack.device)
+                    gi = ops.angle_stack(s_stack, full)                                 # G is symmetric: rows = columns
+                    st["s_stack"], st["s_colnorm"], st["s_rotations"] = gi, ops.jacobi_onesided(gi, d_s), True
+                elif stud_jacobi:
                     st["s_stack"], st["s_colnorm"] = s_stack, ops.jacobi_onesided(s_stack, d_s)
                 else:
                     s_ts = ops.tridiagonalise(s_stack)
@@ -848,7 +857,12 @@ class GrassmannianLayerSelector(nn.Module):
         ss = st["student_stream"]
         cur = torch.cuda.current_stream()
         with torch.cuda.stream(ss if ss is not None else cur):
-            if st["stud_jacobi"]:
+            if st["stud_jacobi"] and st.get("s_rotations"):
+                # [G J ; J]: eigenvalues = column norms of the top half, eigenvectors = columns of the bottom half
+                order = st["s_colnorm"].argsort(dim=1, descending=True, stable=True)
+                lam_s = st["s_colnorm"].gather(1, order)
+                v_all = st["s_stack"][:, :, d_s:].gather(1, order.unsqueeze(2).expand(-1, -1, d_s))
+            elif st["stud_jacobi"]:
                 lam_s, v_all = ops.sort_extract(st["s_stack"], st["s_colnorm"], n_stud)
             else:
                 lam_s = st["s_ts"].vals

@@ -426,7 +426,8 @@ def tridiag_apply_q(ts: TridiagState, x: torch.Tensor, transpose: bool) -> torch
 
 def tridiag_shifted_solve(ts: TridiagState, shifts: torch.Tensor, rhs: torch.Tensor) -> torch.Tensor:
     """x[z][t] = (T_z - shifts[z][t] I)^{-1} rhs[z][t]  (rhs (batch, k, n) in the tridiagonal's basis; the shifts are
-    eigenvalues: LU with partial pivoting, tiny pivots perturbed -- project the singular direction out afterwards)."""
+    eigenvalues: LU with partial pivoting of the row-permuted T - shift I plus single entries of at most eps ||T|| --
+    project the singular direction out afterwards)."""
     batch, k, n = rhs.shape
     assert rhs.is_contiguous() and shifts.dtype == torch.float32 and shifts.shape[0] == batch and shifts.stride(1) == 1
     out = torch.empty_like(rhs)

@@ -1959,10 +1959,24 @@ __global__ void __launch_bounds__(1024) tridiag_mp_rank_kernel(const float* __re
 
 // ---------------------------------------------------------------------------
 // x = (T - shift I)^{-1} rhs for k right-hand sides per tridiagonal, each with its own shift that IS (to round-off)
-// an eigenvalue of T: slagtf LU with partial pivoting + ONE slagts-style solve with the pivot perturbation that
-// inverse iteration uses, so the answer is finite: rhs's component along the shift's own eigenvector is amplified
-// by at most 1 / (eps ||T||) -- the caller projects that direction out (it asks for the solve on the orthogonal
-// complement).  Same thread-per-vector LDS layout as tridiag_invit_kernel.  grid = (ceil(k/vpw), batch), block 64.
+// an eigenvalue of T: slagtf LU with partial pivoting + ONE solve.  The answer is finite: rhs's component along the
+// shift's own eigenvector is amplified by at most about 1 / (eps ||T||) -- the caller projects that direction out (it
+// asks for the solve on the orthogonal complement).
+//   Where the singularity is removed.  The entry that the elimination has reduced to less than eps ||T|| in the pivot
+// position is set to +-eps ||T|| BEFORE it is compared with the sub-diagonal entry and before any multiplier is formed
+// from it, so the factors are exactly those of P (T - shift I) + E, P the row interchanges made so far and E one
+// entry of at most eps ||T|| per replacement (a diagonal entry of T where no interchange precedes it, the entry
+// (i, i + 1) after one): a change the complement solve feels as eps ||T|| / gap.  slagts's way -- factor first, replace small pivots during the back substitution --
+// is not such a change when T is nearly reducible: at the end of the block that owns the eigenvalue the reduced
+// diagonal is about 0, a coupling entry g below it that is tiny but not zero wins the pivot comparison, the multiplier
+// 0 / g or eps ||T|| / g is kept, and the pivot that is replaced later is g, an OFF-diagonal entry (twice, when the
+// reduced diagonal was exactly 0).  With d = [43, 46, 2, 2, ...], e = [2, g, g, ...] (n = 45, shift 47, the block's
+// elimination is exact) the solution came out with 1e-1 ... 1e-3 relative error on the complement for g from 2^-50 to
+// 2^-23 of ||T|| that way, and at 2^-20, where no pivot is below the threshold at all, the exact 0 stayed in the
+// factors and cost 6e-6 (2e-5 at n = 200), against eps ||T|| / gap = 1e-6.  Whether a block whose entries are not
+// fp32 numbers meets the same fate depends on the round-off residue left in the reduced diagonal, hence on whether
+// a - m * b is contracted.  The back substitution keeps a floor of eps^2 ||T|| against a division by zero only.
+// Same thread-per-vector LDS layout as tridiag_invit_kernel.  grid = (ceil(k/vpw), batch), block 64.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) tridiag_shifted_solve_kernel(const float* __restrict__ d,
                                                                    const float* __restrict__ e,
@@ -1997,8 +2011,9 @@ __global__ void __launch_bounds__(64) tridiag_shifted_solve_kernel(const float* 
         in[i * vpw] = 0.f;
         x[i * vpw] = r[i];
     }
-    {   // slagtf
+    {   // slagtf on P (T - shift I) + E (see above)
         float ai = a[0];
+        if (fabsf(ai) < tol) { ai = copysignf(tol, ai); a[0] = ai; }
         float scale1 = fabsf(ai) + (n > 1 ? fabsf(b[0]) : 0.f);
         for (int i = 0; i < n - 1; ++i) {
             const float ci = c[i * vpw], bi = b[i * vpw];
@@ -2024,6 +2039,7 @@ __global__ void __launch_bounds__(64) tridiag_shifted_solve_kernel(const float* 
                 b[i * vpw] = a1;
                 c[i * vpw] = mult;
             }
+            if (fabsf(a_next) < tol) a_next = copysignf(tol, a_next);
             a[(i + 1) * vpw] = a_next;
             ai = a_next;
             scale1 = scale2;
@@ -2041,13 +2057,14 @@ __global__ void __launch_bounds__(64) tridiag_shifted_solve_kernel(const float* 
         prev = next;
     }
     x[(n - 1) * vpw] = prev;
-    // back substitution (U) with perturbed tiny pivots
+    // back substitution (U); a pivot below the floor can only be an interchanged sub-diagonal entry
+    const float pfloor = fmaxf(eps * tol, 1e-37f);
     float x1 = 0.f, x2 = 0.f;
     float* out = X + ((long)z * k + t) * n;
     for (int i = n - 1; i >= 0; --i) {
         float tmp = x[i * vpw] - b[i * vpw] * x1 - d2[i * vpw] * x2;
         float ak = a[i * vpw];
-        if (fabsf(ak) < tol) ak = copysignf(tol, ak == 0.f ? 1.f : ak);
+        if (fabsf(ak) < pfloor) ak = copysignf(pfloor, ak);
         tmp /= ak;
         out[i] = tmp;
         x2 = x1;
