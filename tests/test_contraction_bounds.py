@@ -162,7 +162,8 @@ def _nt_data(M, N, K, batch, amax, key, row_scale=True):
 @pytest.mark.parametrize("layout", NT_LAYOUTS)
 @pytest.mark.parametrize("M,N,K", NT_SHAPES)
 def test_gemm_nt_integer_exact(dev, path, M, N, K, layout):
-    """C = A B^T bit for bit.  Kernel instance reached (gemm_nt_split_kernel on path 1, gemm_nt_kernel on path 0):
+    """C = A B^T bit for bit.  Instance of gemm_nt_kernel<Path, TA, VEC_A> reached (Path = SplitBf16 on path 1, Fp32Mfma
+    on path 0; <TA, VEC_A> below):
     contig      <float, VEC> where K % 4 == 0 (64, 40), else <float, !VEC> (row stride no multiple of 4)
     padded      <float, VEC> at every K: ragged last K chunk of the 16-byte loader (K = 1, 31, 33, 101, 40)
     offset1     <float, !VEC>: base pointer off by one float, strides aligned
@@ -265,6 +266,8 @@ TN_CASES = [(kr, M, N, v) for (kr, M, N) in [(1, 1, 1), (31, 127, 129), (33, 130
                                              (2592, 8, 8)]
             for v in ["plain", "means", "padded_means", "offset1", "bf16", "bf16_means"]
             + (["tok49", "tok49_cls", "tok49_cls_padded"] if kr == 245 else [])]
+# appended, never inserted: the index of a case seeds its data
+TN_CASES += [(kr, M, N, v) for (kr, M, N) in [(31, 127, 129), (245, 129, 130)] for v in ["chan", "bf16_chan"]]
 
 
 def _tn_data(kr, M, N, bf16, means, key):
@@ -288,12 +291,15 @@ def _tn_data(kr, M, N, bf16, means, key):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kr,M,N,variant", TN_CASES)
 def test_gemm_tn_integer_exact(dev, path, kr, M, N, variant):
-    """C = 0.5 (A - 1 mean_a^T)^T (B - 1 mean_b^T) bit for bit (gemm_tn_split_kernel on path 1, gemm_tn_kernel on 0).
+    """C = 0.5 (A - 1 mean_a^T)^T (B - 1 mean_b^T) bit for bit: gemm_tn_kernel<Path, T, VEC> with Path = SplitBf16 on
+    path 1, Fp32Mfma on path 0; <T, VEC> below.
     plain / means     contiguous: <float, VEC> at (520, 64, 260) and (2592, 8, 8), else <float, !VEC> (column counts
                       that are no multiple of 4 make the row stride one)
     padded_means      <float, VEC> with column counts 127, 129, 130: ragged last column tile of the 16-byte loader
     offset1           <float, !VEC>: bases off by one float
     bf16, bf16_means  <bf16, VEC>
+    chan, bf16_chan   channel-major storage of both operands (column stride != 1) at (31, 127, 129) and (245, 129, 130):
+                      <float, !VEC> with sd != 1 and <bf16, !VEC>, the latter reached by no other exact case
     tok49*            (5, 49, .) token views, CLS-sliced from (5, 50, .): rows_per_batch % 4 != 0, the 4-row groups
                       straddle batch items (tn_row), both loaders (`_padded`: VEC)
     (520, 64, 260): two K-splits (basd_gemm_tn_splits = 2), 17 chunks: the second split ends in a ragged chunk;
@@ -314,8 +320,10 @@ def test_gemm_tn_integer_exact(dev, path, kr, M, N, variant):
         b_arg = _place_tokens(B.to(dt), 49, dev, cls="cls" in variant, layout=lay)
         assert a_arg.shape == (5, 49, M)
     else:
-        lay = {"padded_means": "padded", "offset1": "offset1"}.get(variant, "contig")
+        lay = {"padded_means": "padded", "offset1": "offset1", "chan": "chan", "bf16_chan": "chan"}.get(variant, "contig")
         a_arg, b_arg = _place(A.to(dt), lay, dev), _place(B.to(dt), lay, dev)
+        if lay == "chan":
+            assert a_arg.stride(1) != 1 and b_arg.stride(1) != 1
     kw = dict(mean_a=mean_a.to(dev), mean_b=mean_b.to(dev)) if means else {}
     out = ops.gemm_tn(a_arg, b_arg, scale=0.5, **kw)
     _eq(out, 0.5 * ref, f"gemm_tn {variant} path {path}")
@@ -366,10 +374,10 @@ def _gram_check(out, x, mu, c, centered, scales, what):
 @pytest.mark.parametrize("kr", [1, 33, 70, 245])
 @pytest.mark.parametrize("cols", [1, 127, 129, 257])
 def test_centered_grams_integer_exact(dev, path, cols, kr, n):
-    """G_z = (X_z - 1 mu_z^T)^T (X_z - 1 mu_z^T) bit for bit and symmetric (syrk_tn_split_kernel / syrk_tn_kernel with
-    syrk_reduce_kernel).  Row stride padded to a multiple of 4: <float, VEC> at column counts 1, 127, 129, 257 (one to
-    three tiles, up to six tile pairs with mirrored off-diagonal ones); kr = 245 is a (5, 49, .) token view (4-row
-    groups straddle items).  n = 8 runs with splits = 1 and 3: units % 8 == 0, the XCD-aware decode of the grid, with
+    """G_z = (X_z - 1 mu_z^T)^T (X_z - 1 mu_z^T) bit for bit and symmetric (syrk_tn_kernel<SplitBf16, ...> /
+    syrk_tn_kernel<Fp32Mfma, ...> with syrk_reduce_kernel).  Row stride padded to a multiple of 4: <float, VEC> at
+    column counts 1, 127, 129, 257 (one to three tiles, up to six tile pairs with mirrored off-diagonal ones); kr = 245
+    is a (5, 49, .) token view (4-row groups straddle items).  n = 8 runs with splits = 1 and 3: units % 8 == 0, the XCD-aware decode of the grid, with
     off-diagonal pairs at 129 and 257 columns; at kr = 33 / 70 the third split of three gets no chunk / a ragged one."""
     from basd_amd import ops
     x, mu, c = _gram_data(kr, cols, n, False, ())

@@ -6,27 +6,43 @@
 //     centred z^T z feeding the thin SVD           src/losses/layer_selector.py:35-36, :90-92 (gemm_tn with mean)
 //     U_s.T @ U_t                                  src/losses/layer_selector.py:99          (gemm_nt)
 //
-// Both kernels use v_mfma_f32_32x32x2_f32 (exact fp32 fma chain, 157 TFLOP/s peak
-// on MI355X): a 128x128 block tile, 4 waves as 2x2, each wave 2x2 MFMA tiles.
+// Three kernel frames, each a 128x128 block tile, 4 waves as 2x2, each wave 2x2 MFMA tiles:
 //
-//   gemm_nt : C[M,N] = A[M,K] * B[N,K]^T     K contiguous in both operands.
-//             LDS image [row][k] padded to 36 floats, fragments by ds_read_b128:
-//             one 16-byte read feeds four k-steps (lane half h takes k = 8g+4h+s,
-//             the same permutation for A and B, so the sum over k is unchanged).
-//   gemm_tn : C[M,N] = A[K,M]^T * B[K,N]     contraction index is the slow one
-//             (Gram matrices over tokens).  LDS image [k/4][m][4] (4x4 register
-//             transposes while staging), fragments by ds_read_b128.  Optional
-//             per-column mean subtraction while staging, split over K with one
-//             slab per split (deterministic reduction by reduce_slabs_kernel).
+//   gemm_nt_kernel : C[M,N] = A[M,K] * B[N,K]^T     K contiguous in both operands.
+//   gemm_tn_kernel : C[M,N] = A[K,M]^T * B[K,N]     contraction index is the slow one
+//             (Gram matrices over tokens).  Optional per-column mean subtraction
+//             while staging, split over K with one slab per split (deterministic
+//             reduction by reduce_slabs_kernel).
+//   syrk_tn_kernel : the symmetric multi-matrix form of gemm_tn (lower tile pairs only).
+//
+// Each frame is a template over an arithmetic policy, which owns the LDS image of an
+// operand tile, its staging store, the MFMA block and the TN epilogue's register map:
+//
+//   Fp32Mfma  : v_mfma_f32_32x32x2_f32 (exact fp32 fma chain, 157 TFLOP/s peak on MI355X).
+//             NT image [row][k] padded to 36 floats, TN image [k/4][m][4] (4x4 register
+//             transposes while staging); fragments by ds_read_b128: one 16-byte read
+//             feeds four k-steps (lane half h takes k = 8g+4h+s, the same permutation
+//             for A and B, so the sum over k is unchanged).
+//   SplitBf16 : v_mfma_f32_32x32x16_bf16 on three-way split operands, fp32 results
+//             (see the policy).  basd_gemm_tuning selects; this one is the default.
+#include <type_traits>
+
 #include "basd_common.h"
 
 namespace basd {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// The MFMA blocks read their fragments through pointers that are LDS pointers by type: with generic pointers the
+// compiler schedules the reads of a block differently once the block is a function of its own (syrk: all reads of a
+// half ahead of its MFMAs instead of interleaved with the MFMAs of the half before).
+template <typename T>
+using lds_ptr = const __attribute__((address_space(3))) T*;
 
 constexpr int BM = 128, BN = 128;
 
-// ---- split operands: fp32-grade products on the bf16 matrix cores (see syrk_tn_split_kernel) ----
+// ---- split operands: fp32-grade products on the bf16 matrix cores (see SplitBf16) ----
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
@@ -81,7 +97,7 @@ __device__ __forceinline__ void store_tile(float* __restrict__ C, long ldc, int 
 }
 
 // ---------------------------------------------------------------------------
-// NT: grid = (ceil(N/128), ceil(M/128), batch), block = 256
+// NT staging: 128 rows x NT_BK contraction steps per operand and chunk, 256 threads
 // ---------------------------------------------------------------------------
 constexpr int NT_BK = 32, NT_LD = 36;
 
@@ -164,108 +180,11 @@ __device__ __forceinline__ void nt_store_lds(float* __restrict__ tile, int tid, 
     }
 }
 
-template <typename TA, bool VEC_A>
-__global__ void __launch_bounds__(256) gemm_nt_kernel(GemmOperand A, GemmOperand B, int M, int N, int K,
-                                                      float* __restrict__ C, long ldc, long c_batch_stride,
-                                                      float scale, const float* __restrict__ bias, float beta,
-                                                      float* __restrict__ colsum_part, int nx, int ny) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * 128 * NT_LD];
-    float* tA = lds;
-    float* tB = lds + 128 * NT_LD;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    // Tile of this workgroup.  1-D grids (gridDim.y == 1 < ny) are decoded XCD-aware: workgroup ids are dealt round-
-    // robin over the 8 XCDs, so the nx column tiles of one row tile get ids of ONE residue class mod 8 and adjacent
-    // slots -- the row tile's A panel (the large, often strided operand) then crosses the fabric into one L2 only
-    // (teacher projection at cfg-2, nx = 3: 464 MB of HBM-side traffic per launch before, for 125 MB of operands).
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (gridDim.y == 1 && ny > 1) {
-        const int r = bx & 7, s = bx >> 3;
-        bx = s % nx;
-        by = (s / nx) * 8 + r;
-        if (by >= ny) return;
-    }
-    const int m0 = by * BM, n0 = bx * BN;
-    A.ptr = (const TA*)A.ptr + (long)blockIdx.z * A.batch_stride;
-    B.ptr = (const float*)B.ptr + (long)blockIdx.z * B.batch_stride;
-    C += (long)blockIdx.z * c_batch_stride;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    float ra[4][4], rb[4][4];
-    long offa[4], offb[4];
-    nt_rows<VEC_A>(A, M, m0, tid, offa);
-    nt_rows<true>(B, N, n0, tid, offb);
-    nt_load<TA, VEC_A>(A, offa, K, 0, tid, ra);
-    nt_load<float, true>(B, offb, K, 0, tid, rb);
-    const int i = lane & 31, h = lane >> 5;
-    for (int k0 = 0; k0 < K; k0 += NT_BK) {
-        __syncthreads();
-        nt_store_lds<VEC_A>(tA, tid, ra);
-        nt_store_lds<true>(tB, tid, rb);
-        __syncthreads();
-        if (k0 + NT_BK < K) {
-            nt_load<TA, VEC_A>(A, offa, K, k0 + NT_BK, tid, ra);
-            nt_load<float, true>(B, offb, K, k0 + NT_BK, tid, rb);
-        }
-#pragma unroll
-        for (int g = 0; g < NT_BK / 8; ++g) {
-            float4 a[2], b[2];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) a[mi] = *(const float4*)(tA + (wm * 64 + mi * 32 + i) * NT_LD + g * 8 + 4 * h);
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) b[ni] = *(const float4*)(tB + (wn * 64 + ni * 32 + i) * NT_LD + g * 8 + 4 * h);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].x, b[ni].x, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].y, b[ni].y, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].z, b[ni].z, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].w, b[ni].w, acc[mi][ni], 0, 0, 0);
-                }
-        }
-    }
-    store_tile(C, ldc, M, N, m0, n0, acc, wm, wn, lane, scale, bias, beta);
-    if (colsum_part) {
-        // column sums of this row tile of C (the values just stored; beta == 0): the caller's column means
-        // then cost one small fold instead of another pass over C.  Fixed order: deterministic.
-        const int col_l = lane & 31, hi = lane >> 5;
-        float s[2] = {0.f, 0.f};
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            const int col = n0 + wn * 64 + ni * 32 + col_l;
-            const float bv = (bias && col < N) ? bias[col] : 0.f;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (row < M) s[ni] += acc[mi][ni][r] * scale - bv;
-                }
-            s[ni] += __shfl_xor(s[ni], 32, 64);      // the two lane halves hold different rows of one column
-        }
-        __syncthreads();                             // the K loop is done with the LDS tiles
-        if (hi == 0) {
-            lds[wm * 128 + wn * 64 + col_l] = s[0];
-            lds[wm * 128 + wn * 64 + 32 + col_l] = s[1];
-        }
-        __syncthreads();
-        if (tid < 128 && n0 + tid < N)
-            colsum_part[((long)blockIdx.z * ny + by) * N + n0 + tid] = lds[tid] + lds[128 + tid];
-    }
-}
-
 // ---------------------------------------------------------------------------
-// NT with split operands (see syrk_tn_split_kernel): both tiles are staged as three bf16 planes [row][k], row stride 40
+// NT with split operands (see SplitBf16): both tiles are staged as three bf16 planes [row][k], row stride 40
 // bf16 = 80 bytes (20 dwords: the 16 lanes of a ds_read_b128 group land on disjoint bank quads), a lane's MFMA operand
-// is ONE 16-byte read of 8 consecutive k.  Rows map to MFMA lanes directly: store_tile and the column-sum epilogue are
-// those of gemm_nt_kernel.  The strided-operand loader (channel-major teacher tokens: lanes along rows) fetches k in
+// is ONE 16-byte read of 8 consecutive k.  Rows map to MFMA lanes directly: store_tile and the column-sum epilogue serve
+// both policies.  The strided-operand loader (channel-major teacher tokens: lanes along rows) fetches k in
 // adjacent PAIRS (k0 + 2 (tid >> 7) + 4 q + {0, 1}) so that a pair packs into one 4-byte LDS store per plane.
 // ---------------------------------------------------------------------------
 constexpr int NTS_LD = 40;                       // bf16 elements per LDS row (32 used)
@@ -331,112 +250,8 @@ __device__ __forceinline__ void nts_store_lds(unsigned short* __restrict__ tile,
     }
 }
 
-template <typename TA, bool VEC_A>
-__global__ void __launch_bounds__(256) gemm_nt_split_kernel(GemmOperand A, GemmOperand B, int M, int N, int K,
-                                                            float* __restrict__ C, long ldc, long c_batch_stride,
-                                                            float scale, const float* __restrict__ bias, float beta,
-                                                            float* __restrict__ colsum_part, int nx, int ny) {
-    __shared__ __attribute__((aligned(16))) unsigned short lds16[2 * 3 * NTS_PLANE];
-    unsigned short* tA = lds16;
-    unsigned short* tB = lds16 + 3 * NTS_PLANE;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    int bx = blockIdx.x, by = blockIdx.y;       // XCD-aware decode of 1-D grids: see gemm_nt_kernel
-    if (gridDim.y == 1 && ny > 1) {
-        const int r = bx & 7, s = bx >> 3;
-        bx = s % nx;
-        by = (s / nx) * 8 + r;
-        if (by >= ny) return;
-    }
-    const int m0 = by * BM, n0 = bx * BN;
-    A.ptr = (const TA*)A.ptr + (long)blockIdx.z * A.batch_stride;
-    B.ptr = (const float*)B.ptr + (long)blockIdx.z * B.batch_stride;
-    C += (long)blockIdx.z * c_batch_stride;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    float ra[4][4], rb[4][4];
-    long offa[4], offb[4];
-    nts_rows<VEC_A>(A, M, m0, tid, offa);
-    nts_rows<true>(B, N, n0, tid, offb);
-    nts_load<TA, VEC_A>(A, offa, K, 0, tid, ra);
-    nts_load<float, true>(B, offb, K, 0, tid, rb);
-    const int i = lane & 31, h = lane >> 5;
-    for (int k0 = 0; k0 < K; k0 += NT_BK) {
-        __syncthreads();
-        nts_store_lds<VEC_A>(tA, tid, ra);
-        nts_store_lds<true>(tB, tid, rb);
-        __syncthreads();
-        if (k0 + NT_BK < K) {
-            nts_load<TA, VEC_A>(A, offa, K, k0 + NT_BK, tid, ra);
-            nts_load<float, true>(B, offb, K, k0 + NT_BK, tid, rb);
-        }
-#pragma unroll
-        for (int s16 = 0; s16 < NT_BK / 16; ++s16) {
-            bf16x8 a[2][3], b[2][3];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-                    a[mi][p] = *(const bf16x8*)(tA + p * NTS_PLANE + (wm * 64 + mi * 32 + i) * NTS_LD + 16 * s16 + 8 * h);
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-                    b[ni][p] = *(const bf16x8*)(tB + p * NTS_PLANE + (wn * 64 + ni * 32 + i) * NTS_LD + 16 * s16 + 8 * h);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    f32x16 c = acc[mi][ni];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][2], b[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][0], c, 0, 0, 0);
-                    acc[mi][ni] = c;
-                }
-        }
-    }
-    store_tile(C, ldc, M, N, m0, n0, acc, wm, wn, lane, scale, bias, beta);
-    if (colsum_part) {       // column sums of this row tile of C: see gemm_nt_kernel
-        float* lds = (float*)lds16;
-        const int col_l = lane & 31, hi = lane >> 5;
-        float s[2] = {0.f, 0.f};
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            const int col = n0 + wn * 64 + ni * 32 + col_l;
-            const float bv = (bias && col < N) ? bias[col] : 0.f;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (row < M) s[ni] += acc[mi][ni][r] * scale - bv;
-                }
-            s[ni] += __shfl_xor(s[ni], 32, 64);
-        }
-        __syncthreads();
-        if (hi == 0) {
-            lds[wm * 128 + wn * 64 + col_l] = s[0];
-            lds[wm * 128 + wn * 64 + 32 + col_l] = s[1];
-        }
-        __syncthreads();
-        if (tid < 128 && n0 + tid < N)
-            colsum_part[((long)blockIdx.z * ny + by) * N + n0 + tid] = lds[tid] + lds[128 + tid];
-    }
-}
-
 // ---------------------------------------------------------------------------
-// TN: grid = (ceil(N/128), ceil(M/128), batch * splits), block = 256
-//   A: (Krows x M), B: (Krows x N); contraction over rows [k_begin, k_end) of the split.
-//   out: slab (split) or batch element: C + z * c_z_stride.
+// TN staging: TN_BK rows x 128 columns per operand and chunk, 128 threads per operand
 // ---------------------------------------------------------------------------
 constexpr int TN_BK = 32;
 
@@ -539,196 +354,8 @@ __device__ __forceinline__ void tn_store_lds(float* __restrict__ tile, int t, co
     }
 }
 
-template <typename T, bool VEC>
-__global__ void __launch_bounds__(256) gemm_tn_kernel(GemmOperand A, GemmOperand B, int M, int N, int Krows,
-                                                      int splits, const float* __restrict__ mean_a,
-                                                      const float* __restrict__ mean_b, float* __restrict__ C,
-                                                      long ldc, long c_z_stride, float scale) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * TN_BK * 128];
-    float* tA = lds;
-    float* tB = lds + TN_BK * 128;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int bz = blockIdx.z / splits, sp = blockIdx.z - bz * splits;
-    A.ptr = (const T*)A.ptr + (long)bz * A.batch_stride;
-    B.ptr = (const T*)B.ptr + (long)bz * B.batch_stride;
-    C += (long)blockIdx.z * c_z_stride;
-    // rows of this split, in multiples of TN_BK
-    const int chunks = (Krows + TN_BK - 1) / TN_BK;
-    const int per = (chunks + splits - 1) / splits;
-    const int k_begin = sp * per * TN_BK;
-    int k_end = k_begin + per * TN_BK;
-    if (k_end > Krows) k_end = Krows;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // threads 0..127 own operand A, 128..255 operand B (wave-uniform split)
-    const bool is_b = tid >= 128;
-    const int t = tid & 127;
-    const GemmOperand& op = is_b ? B : A;
-    const int cols = is_b ? N : M, col0 = is_b ? n0 : m0;
-    const float* mean = is_b ? mean_b : mean_a;
-    float* tile = is_b ? tB : tA;
-    float reg[2][4][4], m4[4];
-    TnCursor cu;
-    tn_cursor_init(cu, op, k_begin, t);
-    tn_mean4(mean, cols, col0, t, m4);
-    if (k_begin < k_end) tn_load<T, VEC>(op, cu, k_end, cols, k_begin, col0, t, m4, reg);
-    const int i = lane & 31, h = lane >> 5;
-    for (int k0 = k_begin; k0 < k_end; k0 += TN_BK) {
-        __syncthreads();
-        tn_store_lds(tile, t, reg, m4);
-        __syncthreads();
-        if (k0 + TN_BK < k_end) {
-            tn_cursor_advance(cu, op);
-            tn_load<T, VEC>(op, cu, k_end, cols, k0 + TN_BK, col0, t, m4, reg);
-        }
-#pragma unroll
-        for (int g = 0; g < TN_BK / 8; ++g) {
-            float4 a[2], b[2];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) a[mi] = *(const float4*)(tA + (((2 * g + h) * 128 + wm * 64 + mi * 32 + i) << 2));
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) b[ni] = *(const float4*)(tB + (((2 * g + h) * 128 + wn * 64 + ni * 32 + i) << 2));
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].x, b[ni].x, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].y, b[ni].y, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].z, b[ni].z, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].w, b[ni].w, acc[mi][ni], 0, 0, 0);
-                }
-        }
-    }
-    store_tile(C, ldc, M, N, m0, n0, acc, wm, wn, lane, scale);
-}
-
-
 // ---------------------------------------------------------------------------
-// Multi-matrix symmetric TN (centred Gram / SYRK):  G[z] = scale[z] * (X_z - 1 mean_z^T)^T (X_z - 1 mean_z^T)
-//   grid = T(T+1)/2 lower-triangular 128x128 tile pairs x splits x n_mats (1-D, decoded XCD-aware), block = 256.
-//   X_z share shape and strides, base pointers come from a device table.  Only tiles (mi >= ni) are
-//   computed; a diagonal tile stages its column slab once and feeds both MFMA operands from it.  Half the
-//   column-slab traffic of the general TN kernel (9 instead of 18 slab reads at 384 columns).
-//   syrk_reduce_kernel folds the split slabs in fixed order and mirrors the strict lower tiles.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void tri_tile(int p, int& mi, int& ni) {
-    mi = 0;
-    while ((mi + 1) * (mi + 2) / 2 <= p) ++mi;
-    ni = p - mi * (mi + 1) / 2;
-}
-
-template <typename T, bool VEC>
-__global__ void __launch_bounds__(256) syrk_tn_kernel(const void* const* __restrict__ ptrs, GemmOperand X, int cols,
-                                                      int Krows, int splits, int n_mats, int pairs,
-                                                      const float* __restrict__ means, float* __restrict__ slabs,
-                                                      const float* __restrict__ fold, int fold_parts, int fold_from) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * TN_BK * 128];
-    // XCD-aware decode of the 1-D grid: workgroup ids that agree mod 8 run on one XCD (one L2).  The tile
-    // pairs of one (matrix, split) unit read the same rows, so they are given ids of one residue class and
-    // adjacent dispatch slots: the unit's rows come over the fabric once, the other pairs hit in that L2
-    // (measured: 975 MB -> see profiles/ per launch at cfg-2 against 308 MB of operands).
-    int pair, unit;
-    {
-        const int units = splits * n_mats, id = blockIdx.x;
-        if ((units & 7) == 0) {
-            const int xcd = id & 7, slot = id >> 3;
-            pair = slot % pairs;
-            unit = xcd + 8 * (slot / pairs);
-        } else {
-            pair = id % pairs;
-            unit = id / pairs;
-        }
-    }
-    int tmi, tni;
-    tri_tile(pair, tmi, tni);
-    const bool diag = tmi == tni;
-    float* tA = lds;
-    float* tB = diag ? lds : lds + TN_BK * 128;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    const int m0 = tmi * BM, n0 = tni * BN;
-    const int z = unit / splits, sp = unit - z * splits;
-    X.ptr = ptrs[z];
-    const float* mean = means ? means + (long)z * cols : nullptr;
-    float* C = slabs + ((long)z * splits + sp) * (long)cols * cols;
-    const int chunks = (Krows + TN_BK - 1) / TN_BK;
-    const int per = (chunks + splits - 1) / splits;
-    const int k_begin = sp * per * TN_BK;
-    int k_end = k_begin + per * TN_BK;
-    if (k_end > Krows) k_end = Krows;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const bool is_b = tid >= 128;
-    const bool loader = !(is_b && diag);       // wave-uniform
-    const int t = tid & 127;
-    const int col0 = is_b ? n0 : m0;
-    float* tile = is_b ? tB : tA;
-    float reg[2][4][4], m4[4];
-    TnCursor cu;
-    tn_cursor_init(cu, X, k_begin, t);
-    if (fold && z >= fold_from) {
-        // column means folded here from the row-tile sums that the producing GEMM's epilogue left behind
-        // (fixed order: deterministic) -- one small kernel less on the teacher chain, which is the step's
-        // critical path and gets its small launches starved by the student chain's long Gram launch
-        const float* fp = fold + (long)(z - fold_from) * fold_parts * cols;
-        const int c = col0 + (t & 31) * 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float s = 0.f;
-            if (c + e < cols)
-                for (int p = 0; p < fold_parts; ++p) s += fp[(long)p * cols + c + e];
-            m4[e] = s * (1.f / Krows);
-        }
-    } else {
-        tn_mean4(mean, cols, col0, t, m4);
-    }
-    if (loader && k_begin < k_end) tn_load<T, VEC>(X, cu, k_end, cols, k_begin, col0, t, m4, reg);
-    const int i = lane & 31, h = lane >> 5;
-    for (int k0 = k_begin; k0 < k_end; k0 += TN_BK) {
-        __syncthreads();
-        if (loader) tn_store_lds(tile, t, reg, m4);
-        __syncthreads();
-        if (loader && k0 + TN_BK < k_end) {
-            tn_cursor_advance(cu, X);
-            tn_load<T, VEC>(X, cu, k_end, cols, k0 + TN_BK, col0, t, m4, reg);
-        }
-#pragma unroll
-        for (int g = 0; g < TN_BK / 8; ++g) {
-            float4 a[2], b[2];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) a[mi] = *(const float4*)(tA + (((2 * g + h) * 128 + wm * 64 + mi * 32 + i) << 2));
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) b[ni] = *(const float4*)(tB + (((2 * g + h) * 128 + wn * 64 + ni * 32 + i) << 2));
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].x, b[ni].x, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].y, b[ni].y, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].z, b[ni].z, acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].w, b[ni].w, acc[mi][ni], 0, 0, 0);
-                }
-        }
-    }
-    store_tile(C, cols, cols, cols, m0, n0, acc, wm, wn, lane, 1.f);
-}
-
-// ---------------------------------------------------------------------------
-// The same Gram launch on the bf16 matrix cores, with fp32 results: "split" operands.
+// The TN image on the bf16 matrix cores, with fp32 results: "split" operands.
 //   fp32 MFMA runs at 157 TF dense on this chip, bf16 MFMA at 2.5 PF.  Every staged value (x - mean, fp32) is cut into
 //   three bf16 pieces hi + mid + lo = x EXACTLY (round-to-nearest pieces of 8 significant bits each: 24 in all), once,
 //   while the slab goes to LDS; a product x y is then the six piece products of order <= 2^-16 (hi hi, hi mid, mid hi,
@@ -761,80 +388,147 @@ __device__ __forceinline__ void tn_store_lds_split(unsigned short* __restrict__ 
     }
 }
 
-template <typename T, bool VEC>
-__global__ void __launch_bounds__(256) syrk_tn_split_kernel(const void* const* __restrict__ ptrs, GemmOperand X, int cols,
-                                                            int Krows, int splits, int n_mats, int pairs,
-                                                            const float* __restrict__ means, float* __restrict__ slabs,
-                                                            const float* __restrict__ fold, int fold_parts, int fold_from) {
-    __shared__ __attribute__((aligned(16))) unsigned short lds[2 * 3 * SPLIT_PLANE];
-    int pair, unit;       // XCD-aware decode: see syrk_tn_kernel
-    {
-        const int units = splits * n_mats, id = blockIdx.x;
-        if ((units & 7) == 0) {
-            const int xcd = id & 7, slot = id >> 3;
-            pair = slot % pairs;
-            unit = xcd + 8 * (slot / pairs);
-        } else {
-            pair = id % pairs;
-            unit = id / pairs;
+// ---------------------------------------------------------------------------
+// Arithmetic policies: what differs between the two paths of a frame, and nothing else.
+//   lds_t, NT_TILE, TN_TILE   element type of the LDS image, elements of one operand tile in the NT / TN image
+//   nt_rows, nt_load          NT loader (the strided form differs: single k per thread / adjacent k pairs)
+//   nt_stage, tn_stage        registers -> LDS image
+//   nt_block, tn_block        fragment reads and MFMAs of one staged chunk (NT_BK / TN_BK contraction steps)
+//   tn_store_c                TN epilogue: accumulator register -> (row, column) of C
+// The order of the MFMAs inside mma() is part of the result's bits.
+// ---------------------------------------------------------------------------
+struct Fp32Mfma {
+    typedef float lds_t;
+    static constexpr int NT_TILE = 128 * NT_LD;
+    static constexpr int TN_TILE = TN_BK * 128;
+
+    template <bool VEC>
+    static __device__ __forceinline__ void nt_rows(const GemmOperand& o, int rows_total, int row0, int tid,
+                                                   long (&off)[4]) {
+        basd::nt_rows<VEC>(o, rows_total, row0, tid, off);
+    }
+    template <typename TA, bool VEC>
+    static __device__ __forceinline__ void nt_load(const GemmOperand& o, const long (&off)[4], int K, int k0, int tid,
+                                                   float (&reg)[4][4]) {
+        basd::nt_load<TA, VEC>(o, off, K, k0, tid, reg);
+    }
+    template <bool VEC>
+    static __device__ __forceinline__ void nt_stage(lds_t* __restrict__ tile, int tid, const float (&reg)[4][4]) {
+        nt_store_lds<VEC>(tile, tid, reg);
+    }
+    static __device__ __forceinline__ void tn_stage(lds_t* __restrict__ tile, int t, const float (&reg)[2][4][4],
+                                                    const float (&m4)[4]) {
+        tn_store_lds(tile, t, reg, m4);
+    }
+
+    // one f32x4 per 32-row block and side: four k-steps
+    static __device__ __forceinline__ void mma(const f32x4 (&a)[2], const f32x4 (&b)[2], f32x16 (&acc)[2][2]) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].x, b[ni].x, acc[mi][ni], 0, 0, 0);
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].y, b[ni].y, acc[mi][ni], 0, 0, 0);
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].z, b[ni].z, acc[mi][ni], 0, 0, 0);
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi].w, b[ni].w, acc[mi][ni], 0, 0, 0);
+            }
+    }
+    static __device__ __forceinline__ void nt_block(lds_ptr<lds_t> tA, lds_ptr<lds_t> tB, int wm, int wn, int lane,
+                                                    f32x16 (&acc)[2][2]) {
+        const int i = lane & 31, h = lane >> 5;
+#pragma unroll
+        for (int g = 0; g < NT_BK / 8; ++g) {
+            f32x4 a[2], b[2];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) a[mi] = *(lds_ptr<f32x4>)(tA + (wm * 64 + mi * 32 + i) * NT_LD + g * 8 + 4 * h);
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) b[ni] = *(lds_ptr<f32x4>)(tB + (wn * 64 + ni * 32 + i) * NT_LD + g * 8 + 4 * h);
+            mma(a, b, acc);
         }
     }
-    int tmi, tni;
-    tri_tile(pair, tmi, tni);
-    const bool diag = tmi == tni;
-    unsigned short* tA = lds;
-    unsigned short* tB = diag ? lds : lds + 3 * SPLIT_PLANE;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    const int m0 = tmi * BM, n0 = tni * BN;
-    const int z = unit / splits, sp = unit - z * splits;
-    X.ptr = ptrs[z];
-    const float* mean = means ? means + (long)z * cols : nullptr;
-    float* C = slabs + ((long)z * splits + sp) * (long)cols * cols;
-    const int chunks = (Krows + TN_BK - 1) / TN_BK;
-    const int per = (chunks + splits - 1) / splits;
-    const int k_begin = sp * per * TN_BK;
-    int k_end = k_begin + per * TN_BK;
-    if (k_end > Krows) k_end = Krows;
-
-    f32x16 acc[2][2];
+    static __device__ __forceinline__ void tn_block(lds_ptr<lds_t> tA, lds_ptr<lds_t> tB, int wm, int wn, int lane,
+                                                    f32x16 (&acc)[2][2]) {
+        const int i = lane & 31, h = lane >> 5;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int g = 0; g < TN_BK / 8; ++g) {
+            f32x4 a[2], b[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+            for (int mi = 0; mi < 2; ++mi) a[mi] = *(lds_ptr<f32x4>)(tA + (((2 * g + h) * 128 + wm * 64 + mi * 32 + i) << 2));
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const bool is_b = tid >= 128;
-    const bool loader = !(is_b && diag);       // wave-uniform
-    const int t = tid & 127;
-    const int col0 = is_b ? n0 : m0;
-    unsigned short* tile = is_b ? tB : tA;
-    float reg[2][4][4], m4[4];
-    TnCursor cu;
-    tn_cursor_init(cu, X, k_begin, t);
-    if (fold && z >= fold_from) {
-        const float* fp = fold + (long)(z - fold_from) * fold_parts * cols;
-        const int c = col0 + (t & 31) * 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float s = 0.f;
-            if (c + e < cols)
-                for (int p = 0; p < fold_parts; ++p) s += fp[(long)p * cols + c + e];
-            m4[e] = s * (1.f / Krows);
+            for (int ni = 0; ni < 2; ++ni) b[ni] = *(lds_ptr<f32x4>)(tB + (((2 * g + h) * 128 + wn * 64 + ni * 32 + i) << 2));
+            mma(a, b, acc);
         }
-    } else {
-        tn_mean4(mean, cols, col0, t, m4);
     }
-    if (loader && k_begin < k_end) tn_load<T, VEC>(X, cu, k_end, cols, k_begin, col0, t, m4, reg);
-    const int i = lane & 31, h = lane >> 5;
-    for (int k0 = k_begin; k0 < k_end; k0 += TN_BK) {
-        __syncthreads();
-        if (loader) tn_store_lds_split(tile, t, reg, m4);
-        __syncthreads();
-        if (loader && k0 + TN_BK < k_end) {
-            tn_cursor_advance(cu, X);
-            tn_load<T, VEC>(X, cu, k_end, cols, k0 + TN_BK, col0, t, m4, reg);
+
+    // rows and columns of the tile map to MFMA lanes directly: store_tile (acc * scale - 0.f, no beta read)
+    static __device__ __forceinline__ void tn_store_c(float* __restrict__ C, long ldc, int M, int N, int m0, int n0,
+                                                      const f32x16 (&acc)[2][2], int wm, int wn, int lane, float scale) {
+        store_tile(C, ldc, M, N, m0, n0, acc, wm, wn, lane, scale);
+    }
+};
+
+struct SplitBf16 {
+    typedef unsigned short lds_t;
+    static constexpr int NT_TILE = 3 * NTS_PLANE;
+    static constexpr int TN_TILE = 3 * SPLIT_PLANE;
+
+    template <bool VEC>
+    static __device__ __forceinline__ void nt_rows(const GemmOperand& o, int rows_total, int row0, int tid,
+                                                   long (&off)[4]) {
+        nts_rows<VEC>(o, rows_total, row0, tid, off);
+    }
+    template <typename TA, bool VEC>
+    static __device__ __forceinline__ void nt_load(const GemmOperand& o, const long (&off)[4], int K, int k0, int tid,
+                                                   float (&reg)[4][4]) {
+        nts_load<TA, VEC>(o, off, K, k0, tid, reg);
+    }
+    template <bool VEC>
+    static __device__ __forceinline__ void nt_stage(lds_t* __restrict__ tile, int tid, const float (&reg)[4][4]) {
+        nts_store_lds<VEC>(tile, tid, reg);
+    }
+    static __device__ __forceinline__ void tn_stage(lds_t* __restrict__ tile, int t, const float (&reg)[2][4][4],
+                                                    const float (&m4)[4]) {
+        tn_store_lds_split(tile, t, reg, m4);
+    }
+
+    // planes (hi, mid, lo) per 32-row block and side, 8 k-steps each: lo hi, hi lo, mid mid, mid hi, hi mid, hi hi
+    static __device__ __forceinline__ void mma(const bf16x8 (&a)[2][3], const bf16x8 (&b)[2][3], f32x16 (&acc)[2][2]) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                f32x16 c = acc[mi][ni];
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][2], b[ni][0], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][2], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][1], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][0], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][1], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][0], c, 0, 0, 0);
+                acc[mi][ni] = c;
+            }
+    }
+    static __device__ __forceinline__ void nt_block(lds_ptr<lds_t> tA, lds_ptr<lds_t> tB, int wm, int wn, int lane,
+                                                    f32x16 (&acc)[2][2]) {
+        const int i = lane & 31, h = lane >> 5;
+#pragma unroll
+        for (int s16 = 0; s16 < NT_BK / 16; ++s16) {
+            bf16x8 a[2][3], b[2][3];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+                    a[mi][p] = *(lds_ptr<bf16x8>)(tA + p * NTS_PLANE + (wm * 64 + mi * 32 + i) * NTS_LD + 16 * s16 + 8 * h);
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+                    b[ni][p] = *(lds_ptr<bf16x8>)(tB + p * NTS_PLANE + (wn * 64 + ni * 32 + i) * NTS_LD + 16 * s16 + 8 * h);
+            mma(a, b, acc);
         }
+    }
+    static __device__ __forceinline__ void tn_block(lds_ptr<lds_t> tA, lds_ptr<lds_t> tB, int wm, int wn, int lane,
+                                                    f32x16 (&acc)[2][2]) {
+        const int i = lane & 31, h = lane >> 5;
 #pragma unroll
         for (int s16 = 0; s16 < TN_BK / 16; ++s16) {
             bf16x8 a[2][3], b[2][3];
@@ -843,133 +537,292 @@ __global__ void __launch_bounds__(256) syrk_tn_split_kernel(const void* const* _
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
-                    a[mi][p] = *(const bf16x8*)(tA + p * SPLIT_PLANE + ((o * 128 + (wm * 2 + mi) * 32 + i) << 3));
+                    a[mi][p] = *(lds_ptr<bf16x8>)(tA + p * SPLIT_PLANE + ((o * 128 + (wm * 2 + mi) * 32 + i) << 3));
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
-                    b[ni][p] = *(const bf16x8*)(tB + p * SPLIT_PLANE + ((o * 128 + (wn * 2 + ni) * 32 + i) << 3));
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    f32x16 c = acc[mi][ni];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][2], b[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][0], c, 0, 0, 0);
-                    acc[mi][ni] = c;
-                }
+                    b[ni][p] = *(lds_ptr<bf16x8>)(tB + p * SPLIT_PLANE + ((o * 128 + (wn * 2 + ni) * 32 + i) << 3));
+            mma(a, b, acc);
         }
     }
-    // epilogue: MFMA lane i of 32-block b holds slab column 4 i + b (rows of C from the A side, columns from the B side)
+
+    // MFMA lane i of 32-block b holds slab column 4 i + b (rows of C from the A side, columns from the B side)
+    static __device__ __forceinline__ void tn_store_c(float* __restrict__ C, long ldc, int M, int N, int m0, int n0,
+                                                      const f32x16 (&acc)[2][2], int wm, int wn, int lane, float scale) {
+        const int i = lane & 31, h = lane >> 5;
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
+        for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            const int col = n0 + 4 * i + (wn * 2 + ni);
-            if (col >= cols) continue;
+            for (int ni = 0; ni < 2; ++ni) {
+                const int col = n0 + 4 * i + (wn * 2 + ni);
+                if (col >= N) continue;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + 4 * ((r & 3) + 8 * (r >> 2) + 4 * h) + (wm * 2 + mi);
-                if (row < cols) C[(long)row * cols + col] = acc[mi][ni][r];
+                for (int r = 0; r < 16; ++r) {
+                    const int row = m0 + 4 * ((r & 3) + 8 * (r >> 2) + 4 * h) + (wm * 2 + mi);
+                    if (row < M) C[(long)row * ldc + col] = acc[mi][ni][r] * scale;
+                }
             }
-        }
+    }
+};
+
+// ---------------------------------------------------------------------------
+// What the frames share, whatever the policy
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 }
 
-// General TN with split operands: gemm_tn_kernel's grid, loaders and splits, syrk_tn_split_kernel's LDS image and MFMA
-// block (column 4 l + e of a slab at position 32 e + l; the epilogue undoes the map on both sides).
-template <typename T, bool VEC>
-__global__ void __launch_bounds__(256) gemm_tn_split_kernel(GemmOperand A, GemmOperand B, int M, int N, int Krows,
-                                                            int splits, const float* __restrict__ mean_a,
-                                                            const float* __restrict__ mean_b, float* __restrict__ C,
-                                                            long ldc, long c_z_stride, float scale) {
-    __shared__ __attribute__((aligned(16))) unsigned short lds[2 * 3 * SPLIT_PLANE];
-    unsigned short* tA = lds;
-    unsigned short* tB = lds + 3 * SPLIT_PLANE;
+// Tile (bx, by) of an NT workgroup; false: an id past the last row tile.  1-D grids (gridDim.y == 1 < ny) are decoded
+// XCD-aware: workgroup ids are dealt round-robin over the 8 XCDs, so the nx column tiles of one row tile get ids of ONE
+// residue class mod 8 and adjacent slots -- the row tile's A panel (the large, often strided operand) then crosses the
+// fabric into one L2 only (teacher projection at cfg-2, nx = 3: 464 MB of HBM-side traffic per launch before, for
+// 125 MB of operands).
+__device__ __forceinline__ bool nt_grid_decode(int nx, int ny, int& bx, int& by) {
+    bx = blockIdx.x;
+    by = blockIdx.y;
+    if (gridDim.y == 1 && ny > 1) {
+        const int r = bx & 7, s = bx >> 3;
+        bx = s % nx;
+        by = (s / nx) * 8 + r;
+        if (by >= ny) return false;
+    }
+    return true;
+}
+
+// (tile pair, unit = matrix x split) of a syrk workgroup.  XCD-aware decode of the 1-D grid: workgroup ids that agree
+// mod 8 run on one XCD (one L2).  The tile pairs of one unit read the same rows, so they are given ids of one residue
+// class and adjacent dispatch slots: the unit's rows come over the fabric once, the other pairs hit in that L2
+// (measured: 975 MB -> see profiles/ per launch at cfg-2 against 308 MB of operands).
+__device__ __forceinline__ void syrk_grid_decode(int units, int pairs, int& pair, int& unit) {
+    const int id = blockIdx.x;
+    if ((units & 7) == 0) {
+        const int xcd = id & 7, slot = id >> 3;
+        pair = slot % pairs;
+        unit = xcd + 8 * (slot / pairs);
+    } else {
+        pair = id % pairs;
+        unit = id / pairs;
+    }
+}
+
+// rows [k_begin, k_end) of K-split sp, in multiples of TN_BK (the last splits may be short or empty)
+__device__ __forceinline__ void tn_split_range(int Krows, int splits, int sp, int& k_begin, int& k_end) {
+    const int chunks = (Krows + TN_BK - 1) / TN_BK;
+    const int per = (chunks + splits - 1) / splits;
+    k_begin = sp * per * TN_BK;
+    k_end = k_begin + per * TN_BK;
+    if (k_end > Krows) k_end = Krows;
+}
+
+// The thread's four column means folded from the row-tile sums that the producing GEMM's epilogue left behind (fixed
+// order: deterministic) -- one small kernel less on the teacher chain, which is the step's critical path and gets its
+// small launches starved by the student chain's long Gram launch.
+__device__ __forceinline__ void tn_fold_mean4(const float* __restrict__ fp, int fold_parts, int cols, int Krows, int col0,
+                                              int t, float (&m4)[4]) {
+    const int c = col0 + (t & 31) * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float s = 0.f;
+        if (c + e < cols)
+            for (int p = 0; p < fold_parts; ++p) s += fp[(long)p * cols + c + e];
+        m4[e] = s * (1.f / Krows);
+    }
+}
+
+// Column sums of this row tile of C (the values just stored; beta == 0): the caller's column means then cost one small
+// fold instead of another pass over C.  Fixed order: deterministic.  `lds`: the tiles' memory, 256 floats are used.
+__device__ __forceinline__ void nt_column_sums(float* lds, const f32x16 (&acc)[2][2], int M, int N, int m0, int n0,
+                                               int wm, int wn, int tid, int lane, float scale,
+                                               const float* __restrict__ bias, float* __restrict__ part) {
+    const int col_l = lane & 31, hi = lane >> 5;
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+        const int col = n0 + wn * 64 + ni * 32 + col_l;
+        const float bv = (bias && col < N) ? bias[col] : 0.f;
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                if (row < M) s[ni] += acc[mi][ni][r] * scale - bv;
+            }
+        s[ni] += __shfl_xor(s[ni], 32, 64);      // the two lane halves hold different rows of one column
+    }
+    __syncthreads();                             // the K loop is done with the LDS tiles
+    if (hi == 0) {
+        lds[wm * 128 + wn * 64 + col_l] = s[0];
+        lds[wm * 128 + wn * 64 + 32 + col_l] = s[1];
+    }
+    __syncthreads();
+    if (tid < 128 && n0 + tid < N) part[n0 + tid] = lds[tid] + lds[128 + tid];
+}
+
+// K loop of the TN frames.  Threads 0..127 stage operand A, 128..255 operand B (wave-uniform), each into `tile`; a
+// thread with loader == false stages nothing (the B side of a diagonal syrk tile, whose tB is tA).
+template <typename Path, typename T, bool VEC>
+__device__ __forceinline__ void tn_main_loop(const GemmOperand& op, TnCursor& cu, bool loader, int k_begin, int k_end,
+                                             int cols, int col0, int t, const float (&m4)[4],
+                                             typename Path::lds_t* tile, const typename Path::lds_t* tA,
+                                             const typename Path::lds_t* tB, int wm, int wn, int lane,
+                                             f32x16 (&acc)[2][2]) {
+    float reg[2][4][4];
+    if (loader && k_begin < k_end) tn_load<T, VEC>(op, cu, k_end, cols, k_begin, col0, t, m4, reg);
+    for (int k0 = k_begin; k0 < k_end; k0 += TN_BK) {
+        __syncthreads();
+        if (loader) Path::tn_stage(tile, t, reg, m4);
+        __syncthreads();
+        if (loader && k0 + TN_BK < k_end) {
+            tn_cursor_advance(cu, op);
+            tn_load<T, VEC>(op, cu, k_end, cols, k0 + TN_BK, col0, t, m4, reg);
+        }
+        Path::tn_block((lds_ptr<typename Path::lds_t>)tA, (lds_ptr<typename Path::lds_t>)tB, wm, wn, lane, acc);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// NT: grid = (ceil(N/128), ceil(M/128), batch) or its 1-D form (nt_grid_decode), block = 256
+// ---------------------------------------------------------------------------
+template <typename Path, typename TA, bool VEC_A>
+__global__ void __launch_bounds__(256) gemm_nt_kernel(GemmOperand A, GemmOperand B, int M, int N, int K,
+                                                      float* __restrict__ C, long ldc, long c_batch_stride,
+                                                      float scale, const float* __restrict__ bias, float beta,
+                                                      float* __restrict__ colsum_part, int nx, int ny) {
+    typedef typename Path::lds_t lds_t;
+    __shared__ __attribute__((aligned(16))) lds_t lds[2 * Path::NT_TILE];
+    lds_t* tA = lds;
+    lds_t* tB = lds + Path::NT_TILE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    int bx, by;
+    if (!nt_grid_decode(nx, ny, bx, by)) return;
+    const int m0 = by * BM, n0 = bx * BN;
+    A.ptr = (const TA*)A.ptr + (long)blockIdx.z * A.batch_stride;
+    B.ptr = (const float*)B.ptr + (long)blockIdx.z * B.batch_stride;
+    C += (long)blockIdx.z * c_batch_stride;
+
+    f32x16 acc[2][2];
+    zero_acc(acc);
+
+    float ra[4][4], rb[4][4];
+    long offa[4], offb[4];
+    Path::template nt_rows<VEC_A>(A, M, m0, tid, offa);
+    Path::template nt_rows<true>(B, N, n0, tid, offb);
+    Path::template nt_load<TA, VEC_A>(A, offa, K, 0, tid, ra);
+    Path::template nt_load<float, true>(B, offb, K, 0, tid, rb);
+    for (int k0 = 0; k0 < K; k0 += NT_BK) {
+        __syncthreads();
+        Path::template nt_stage<VEC_A>(tA, tid, ra);
+        Path::template nt_stage<true>(tB, tid, rb);
+        __syncthreads();
+        if (k0 + NT_BK < K) {
+            Path::template nt_load<TA, VEC_A>(A, offa, K, k0 + NT_BK, tid, ra);
+            Path::template nt_load<float, true>(B, offb, K, k0 + NT_BK, tid, rb);
+        }
+        Path::nt_block((lds_ptr<lds_t>)tA, (lds_ptr<lds_t>)tB, wm, wn, lane, acc);
+    }
+    store_tile(C, ldc, M, N, m0, n0, acc, wm, wn, lane, scale, bias, beta);
+    if (colsum_part)
+        nt_column_sums((float*)lds, acc, M, N, m0, n0, wm, wn, tid, lane, scale, bias,
+                       colsum_part + ((long)blockIdx.z * ny + by) * N);
+}
+
+// ---------------------------------------------------------------------------
+// TN: grid = (ceil(N/128), ceil(M/128), batch * splits), block = 256
+//   A: (Krows x M), B: (Krows x N); contraction over rows [k_begin, k_end) of the split.
+//   out: slab (split) or batch element: C + z * c_z_stride.
+// ---------------------------------------------------------------------------
+template <typename Path, typename T, bool VEC>
+__global__ void __launch_bounds__(256) gemm_tn_kernel(GemmOperand A, GemmOperand B, int M, int N, int Krows,
+                                                      int splits, const float* __restrict__ mean_a,
+                                                      const float* __restrict__ mean_b, float* __restrict__ C,
+                                                      long ldc, long c_z_stride, float scale) {
+    typedef typename Path::lds_t lds_t;
+    __shared__ __attribute__((aligned(16))) lds_t lds[2 * Path::TN_TILE];
+    lds_t* tA = lds;
+    lds_t* tB = lds + Path::TN_TILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
     const int bz = blockIdx.z / splits, sp = blockIdx.z - bz * splits;
     A.ptr = (const T*)A.ptr + (long)bz * A.batch_stride;
     B.ptr = (const T*)B.ptr + (long)bz * B.batch_stride;
     C += (long)blockIdx.z * c_z_stride;
-    const int chunks = (Krows + TN_BK - 1) / TN_BK;
-    const int per = (chunks + splits - 1) / splits;
-    const int k_begin = sp * per * TN_BK;
-    int k_end = k_begin + per * TN_BK;
-    if (k_end > Krows) k_end = Krows;
+    int k_begin, k_end;
+    tn_split_range(Krows, splits, sp, k_begin, k_end);
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const bool is_b = tid >= 128;
     const int t = tid & 127;
     const GemmOperand& op = is_b ? B : A;
     const int cols = is_b ? N : M, col0 = is_b ? n0 : m0;
-    const float* mean = is_b ? mean_b : mean_a;
-    unsigned short* tile = is_b ? tB : tA;
-    float reg[2][4][4], m4[4];
+    float m4[4];
     TnCursor cu;
     tn_cursor_init(cu, op, k_begin, t);
-    tn_mean4(mean, cols, col0, t, m4);
-    if (k_begin < k_end) tn_load<T, VEC>(op, cu, k_end, cols, k_begin, col0, t, m4, reg);
-    const int i = lane & 31, h = lane >> 5;
-    for (int k0 = k_begin; k0 < k_end; k0 += TN_BK) {
-        __syncthreads();
-        tn_store_lds_split(tile, t, reg, m4);
-        __syncthreads();
-        if (k0 + TN_BK < k_end) {
-            tn_cursor_advance(cu, op);
-            tn_load<T, VEC>(op, cu, k_end, cols, k0 + TN_BK, col0, t, m4, reg);
-        }
-#pragma unroll
-        for (int s16 = 0; s16 < TN_BK / 16; ++s16) {
-            bf16x8 a[2][3], b[2][3];
-            const int o = 2 * s16 + h;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-                    a[mi][p] = *(const bf16x8*)(tA + p * SPLIT_PLANE + ((o * 128 + (wm * 2 + mi) * 32 + i) << 3));
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-                    b[ni][p] = *(const bf16x8*)(tB + p * SPLIT_PLANE + ((o * 128 + (wn * 2 + ni) * 32 + i) << 3));
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    f32x16 c = acc[mi][ni];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][2], b[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][0], c, 0, 0, 0);
-                    acc[mi][ni] = c;
-                }
-        }
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            const int col = n0 + 4 * i + (wn * 2 + ni);
-            if (col >= N) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + 4 * ((r & 3) + 8 * (r >> 2) + 4 * h) + (wm * 2 + mi);
-                if (row < M) C[(long)row * ldc + col] = acc[mi][ni][r] * scale;
-            }
-        }
+    tn_mean4(is_b ? mean_b : mean_a, cols, col0, t, m4);
+    tn_main_loop<Path, T, VEC>(op, cu, true, k_begin, k_end, cols, col0, t, m4, is_b ? tB : tA, tA, tB, wm, wn, lane, acc);
+    Path::tn_store_c(C, ldc, M, N, m0, n0, acc, wm, wn, lane, scale);
+}
+
+// ---------------------------------------------------------------------------
+// Multi-matrix symmetric TN (centred Gram / SYRK):  G[z] = scale[z] * (X_z - 1 mean_z^T)^T (X_z - 1 mean_z^T)
+//   grid = T(T+1)/2 lower-triangular 128x128 tile pairs x splits x n_mats (1-D, syrk_grid_decode), block = 256.
+//   X_z share shape and strides, base pointers come from a device table.  Only tiles (mi >= ni) are
+//   computed; a diagonal tile stages its column slab once and feeds both MFMA operands from it.  Half the
+//   column-slab traffic of the general TN kernel (9 instead of 18 slab reads at 384 columns).
+//   syrk_reduce_kernel folds the split slabs in fixed order and mirrors the strict lower tiles.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void tri_tile(int p, int& mi, int& ni) {
+    mi = 0;
+    while ((mi + 1) * (mi + 2) / 2 <= p) ++mi;
+    ni = p - mi * (mi + 1) / 2;
+}
+
+template <typename Path, typename T, bool VEC>
+__global__ void __launch_bounds__(256) syrk_tn_kernel(const void* const* __restrict__ ptrs, GemmOperand X, int cols,
+                                                      int Krows, int splits, int n_mats, int pairs,
+                                                      const float* __restrict__ means, float* __restrict__ slabs,
+                                                      const float* __restrict__ fold, int fold_parts, int fold_from) {
+    typedef typename Path::lds_t lds_t;
+    __shared__ __attribute__((aligned(16))) lds_t lds[2 * Path::TN_TILE];
+    int pair, unit;
+    syrk_grid_decode(splits * n_mats, pairs, pair, unit);
+    int tmi, tni;
+    tri_tile(pair, tmi, tni);
+    const bool diag = tmi == tni;
+    lds_t* tA = lds;
+    lds_t* tB = diag ? lds : lds + Path::TN_TILE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int m0 = tmi * BM, n0 = tni * BN;
+    const int z = unit / splits, sp = unit - z * splits;
+    X.ptr = ptrs[z];
+    const float* mean = means ? means + (long)z * cols : nullptr;
+    float* C = slabs + ((long)z * splits + sp) * (long)cols * cols;
+    int k_begin, k_end;
+    tn_split_range(Krows, splits, sp, k_begin, k_end);
+
+    f32x16 acc[2][2];
+    zero_acc(acc);
+
+    const bool is_b = tid >= 128;
+    const bool loader = !(is_b && diag);       // wave-uniform
+    const int t = tid & 127;
+    const int col0 = is_b ? n0 : m0;
+    float m4[4];
+    TnCursor cu;
+    tn_cursor_init(cu, X, k_begin, t);
+    if (fold && z >= fold_from)
+        tn_fold_mean4(fold + (long)(z - fold_from) * fold_parts * cols, fold_parts, cols, Krows, col0, t, m4);
+    else
+        tn_mean4(mean, cols, col0, t, m4);
+    tn_main_loop<Path, T, VEC>(X, cu, loader, k_begin, k_end, cols, col0, t, m4, is_b ? tB : tA, tA, tB, wm, wn, lane, acc);
+    Path::tn_store_c(C, cols, cols, cols, m0, n0, acc, wm, wn, lane, 1.f);
 }
 
 // grid = (tile pairs * 64, n_mats), block 256: one element of a lower tile per thread.
@@ -1115,6 +968,26 @@ using namespace basd;
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// The one place that picks an MFMA kernel instantiation from (arithmetic path, dtype code, loader form): calls
+// f(Path{}, elem<T>{}, std::bool_constant<VEC>{}); false for an unknown dtype (nothing is launched).
+template <typename T>
+struct elem { typedef T type; };
+
+template <typename F>
+static bool dispatch_mfma(int split, int dtype, bool vec, F&& f) {
+    auto with_elem = [&](auto path, auto el) {
+        if (vec) f(path, el, std::true_type{});
+        else f(path, el, std::false_type{});
+    };
+    auto with_path = [&](auto path) {
+        if (dtype == BASD_DTYPE_F32) with_elem(path, elem<float>{});
+        else if (dtype == BASD_DTYPE_BF16) with_elem(path, elem<__hip_bfloat16>{});
+        else return false;
+        return true;
+    };
+    return split ? with_path(SplitBf16{}) : with_path(Fp32Mfma{});
+}
+
 template <typename T>
 static void launch_colsum(const GemmOperand& X, const void* const* ptrs, const void* x, int rows, int cols, int parts,
                           int batch, bool vec, float* partial, hipStream_t stream) {
@@ -1128,7 +1001,7 @@ extern "C" {
 
 // C[z] (M x N, ldc) = beta * C[z] + scale * A[z] (M x K) * B[z]^T (N x K) - 1 bias^T.
 // Test / tuning hook: 1 (default) = Gram launches and NT products on the bf16 matrix cores with three-way split operands
-// (fp32 results: syrk_tn_split_kernel, gemm_nt_split_kernel); 0 = fp32 MFMA.  Process-wide.
+// (fp32 results: the SplitBf16 instantiations of the three frames); 0 = fp32 MFMA (Fp32Mfma).  Process-wide.
 static int g_gemm_split = 1;
 int basd_gemm_tuning_get(void) { return g_gemm_split; }
 int basd_gemm_tuning(int split_bf16) {
@@ -1153,23 +1026,14 @@ int basd_gemm_nt(const void* a, int a_dtype, long a_sb, long a_sn, long a_sd, in
     // many row tiles x several column tiles: 1-D grid with the XCD-aware decode (see the kernel); else the plain 3-D grid
     const bool xcd = nx > 1 && ny >= 16;
     const dim3 grid = xcd ? dim3(8 * nx * ((ny + 7) / 8), 1, batch) : dim3(nx, ny, batch);
-    if (g_gemm_split && a_dtype == BASD_DTYPE_F32) {
-        const bool vec = a_sd == 1 && aligned16(a) && a_sb % 4 == 0 && a_sn % 4 == 0 && a_batch_stride % 4 == 0;
-        if (vec) gemm_nt_split_kernel<float, true><<<grid, 256, 0, stream>>>(A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
-        else gemm_nt_split_kernel<float, false><<<grid, 256, 0, stream>>>(A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
-    } else if (g_gemm_split && a_dtype == BASD_DTYPE_BF16) {
-        if (a_sd == 1) gemm_nt_split_kernel<__hip_bfloat16, true><<<grid, 256, 0, stream>>>(A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
-        else gemm_nt_split_kernel<__hip_bfloat16, false><<<grid, 256, 0, stream>>>(A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
-    } else if (a_dtype == BASD_DTYPE_F32) {
-        const bool vec = a_sd == 1 && aligned16(a) && a_sb % 4 == 0 && a_sn % 4 == 0 && a_batch_stride % 4 == 0;
-        if (vec) gemm_nt_kernel<float, true><<<grid, 256, 0, stream>>>(A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
-        else gemm_nt_kernel<float, false><<<grid, 256, 0, stream>>>(A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
-    } else if (a_dtype == BASD_DTYPE_BF16) {
-        if (a_sd == 1) gemm_nt_kernel<__hip_bfloat16, true><<<grid, 256, 0, stream>>>(A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
-        else gemm_nt_kernel<__hip_bfloat16, false><<<grid, 256, 0, stream>>>(A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
-    } else {
-        return BASD_EINVAL;
-    }
+    const bool vec = a_dtype == BASD_DTYPE_F32
+                         ? a_sd == 1 && aligned16(a) && a_sb % 4 == 0 && a_sn % 4 == 0 && a_batch_stride % 4 == 0
+                         : a_sd == 1;
+    const bool known = dispatch_mfma(g_gemm_split, a_dtype, vec, [&](auto path, auto el, auto v) {
+        gemm_nt_kernel<decltype(path), typename decltype(el)::type, decltype(v)::value><<<grid, 256, 0, stream>>>(
+            A, B, M, N, K, c, ldc, c_batch_stride, scale, bias, beta, colsum_part, nx, ny);
+    });
+    if (!known) return BASD_EINVAL;
     if (col_mean)      // fold the row-tile sums: col_mean[z][n] = (1/M) sum over the row tiles
         colsum_final_kernel<<<dim3((N + 63) / 64, batch), 256, 0, stream>>>(colsum_part, N, (M + BM - 1) / BM, 1.f / M, col_mean);
     BASD_RETURN_LAST();
@@ -1202,21 +1066,12 @@ int basd_gemm_tn(const void* a, const void* b, int dtype, long a_sb, long a_sn, 
     const bool vec = dtype == BASD_DTYPE_F32 && a_sd == 1 && b_sd == 1 && aligned16(a) && aligned16(b) &&
                      a_sb % 4 == 0 && a_sn % 4 == 0 && b_sb % 4 == 0 && b_sn % 4 == 0 && a_batch_stride % 4 == 0 &&
                      b_batch_stride % 4 == 0;
-    if (g_gemm_split && dtype == BASD_DTYPE_F32) {
-        if (vec) gemm_tn_split_kernel<float, true><<<grid, 256, 0, stream>>>(A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
-        else gemm_tn_split_kernel<float, false><<<grid, 256, 0, stream>>>(A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
-    } else if (g_gemm_split && dtype == BASD_DTYPE_BF16) {
-        if (a_sd == 1 && b_sd == 1) gemm_tn_split_kernel<__hip_bfloat16, true><<<grid, 256, 0, stream>>>(A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
-        else gemm_tn_split_kernel<__hip_bfloat16, false><<<grid, 256, 0, stream>>>(A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
-    } else if (dtype == BASD_DTYPE_F32) {
-        if (vec) gemm_tn_kernel<float, true><<<grid, 256, 0, stream>>>(A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
-        else gemm_tn_kernel<float, false><<<grid, 256, 0, stream>>>(A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
-    } else if (dtype == BASD_DTYPE_BF16) {
-        if (a_sd == 1 && b_sd == 1) gemm_tn_kernel<__hip_bfloat16, true><<<grid, 256, 0, stream>>>(A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
-        else gemm_tn_kernel<__hip_bfloat16, false><<<grid, 256, 0, stream>>>(A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
-    } else {
-        return BASD_EINVAL;
-    }
+    const bool known = dispatch_mfma(g_gemm_split, dtype, dtype == BASD_DTYPE_F32 ? vec : a_sd == 1 && b_sd == 1,
+                                     [&](auto path, auto el, auto v) {
+        gemm_tn_kernel<decltype(path), typename decltype(el)::type, decltype(v)::value><<<grid, 256, 0, stream>>>(
+            A, B, M, N, krows, splits, mean_a, mean_b, out, out_ld, z_stride, k_scale);
+    });
+    if (!known) return BASD_EINVAL;
     if (splits > 1) {
         const long count = (long)M * N;
         int blocks = (int)((count + 255) / 256);
@@ -1291,23 +1146,12 @@ int basd_syrk_multi(const void* const* x_ptrs, int dtype, long sb, long sn, long
     GemmOperand X{nullptr, sb, sn, sd, rows_per_batch, 0};
     const int tiles = (cols + BM - 1) / BM, pairs = tiles * (tiles + 1) / 2;
     const dim3 grid(pairs * splits * n_mats);
-    if (g_gemm_split && dtype == BASD_DTYPE_F32) {
-        const bool vec = vec_ok && sd == 1 && sb % 4 == 0 && sn % 4 == 0;
-        if (vec) syrk_tn_split_kernel<float, true><<<grid, 256, 0, stream>>>(x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
-        else syrk_tn_split_kernel<float, false><<<grid, 256, 0, stream>>>(x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
-    } else if (g_gemm_split && dtype == BASD_DTYPE_BF16) {
-        if (sd == 1) syrk_tn_split_kernel<__hip_bfloat16, true><<<grid, 256, 0, stream>>>(x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
-        else syrk_tn_split_kernel<__hip_bfloat16, false><<<grid, 256, 0, stream>>>(x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
-    } else if (dtype == BASD_DTYPE_F32) {
-        const bool vec = vec_ok && sd == 1 && sb % 4 == 0 && sn % 4 == 0;
-        if (vec) syrk_tn_kernel<float, true><<<grid, 256, 0, stream>>>(x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
-        else syrk_tn_kernel<float, false><<<grid, 256, 0, stream>>>(x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
-    } else if (dtype == BASD_DTYPE_BF16) {
-        if (sd == 1) syrk_tn_kernel<__hip_bfloat16, true><<<grid, 256, 0, stream>>>(x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
-        else syrk_tn_kernel<__hip_bfloat16, false><<<grid, 256, 0, stream>>>(x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
-    } else {
-        return BASD_EINVAL;
-    }
+    const bool vec = dtype == BASD_DTYPE_F32 ? vec_ok && sd == 1 && sb % 4 == 0 && sn % 4 == 0 : sd == 1;
+    const bool known = dispatch_mfma(g_gemm_split, dtype, vec, [&](auto path, auto el, auto v) {
+        syrk_tn_kernel<decltype(path), typename decltype(el)::type, decltype(v)::value><<<grid, 256, 0, stream>>>(
+            x_ptrs, X, cols, krows, splits, n_mats, pairs, means, slabs, fold, fold_parts, fold_from);
+    });
+    if (!known) return BASD_EINVAL;
     syrk_reduce_kernel<<<dim3(pairs * 64, n_mats), 256, 0, stream>>>(slabs, cols, splits, scales, out, out_stride);
     BASD_RETURN_LAST();
 }
