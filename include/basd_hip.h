@@ -109,8 +109,9 @@ int basd_jacobi_workspace_ints(int batch, int max_sweeps);
 /* Longest column (rows_dot; riding rows likewise) basd_jacobi_onesided has a kernel shape for, hence also the largest
  * order of a plain square problem. */
 int basd_jacobi_max_rows(void);
-/* 1 when basd_jacobi_onesided takes large batches of plain n x n matrices with 4 lanes per column pair in LDS (orders
- * 40..144): basd_procrustes_forward_fused then solves the TRANSPOSED cores, without riding rows. */
+/* 1 when the plain 4-lane LDS shape of basd_jacobi_onesided fits order n (39..196; the planner's answer with 4 lanes
+ * forced and the round-robin ordering, whatever the batch: callers test batch >= 128 themselves):
+ * basd_procrustes_forward_fused then solves the TRANSPOSED cores, without riding rows. */
 int basd_jacobi_plain4_fits(int n);
 
 /* In-place one-sided Jacobi on `batch` column-major matrices (rows_tot x n, leading dim rows_tot):
@@ -134,6 +135,13 @@ int basd_jacobi_ordering(int odd_even);
 int basd_jacobi_onesided(float* W, long batch_stride, int rows_dot, int rows_tot, int n, int batch,
                          const int* n_arr, float* colnorm, int colnorm_stride, int max_sweeps, float tol_cos,
                          int* flags, int* sweeps_out, hipStream_t stream);
+/* What basd_jacobi_onesided would launch for that shape under the current tuning hooks (host only, no HIP call).
+ * out8: route -- 1 stacked 8-lane LDS, 2 stacked 4-lane LDS, 3 plain 8-lane LDS, 4 odd-even in registers, 5 plain
+ * 4-lane LDS, 6 16-lane LDS, 7 block rounds, 0 no kernel shape (BASD_EUNSUPPORTED) --, lanes per column pair, elements
+ * per lane, of which over the dot rows, threads, dynamic LDS bytes, and on the block route columns per block and
+ * blocks.  basd_jacobi_plain4_fits / basd_jacobi_lds_square_fits / basd_jacobi_twopass_workspace_bytes answer from the
+ * same planner. */
+int basd_jacobi_plan_query(int rows_dot, int rows_tot, int n, int batch, int per_matrix_orders, int* out8);
 
 /* The same for stacked square cores [M; L_b] (2n x n, leading dimension 2n; the Procrustes cores of relational.py:48)
  * whose 2n rows do not fit LDS while n rows do (n = 129..196: cfg-5's 144, cfg-4's 196): pass 1 solves the top n x n

@@ -26,10 +26,24 @@
 //     matrix flag so that the launches queued for later sweeps return at once.
 #include "basd_common.h"
 
+#include <type_traits>
+
 namespace basd {
 
 // (4 eps)^2: squared relative size below which a column is numerically null
 constexpr float kNull2 = 2.2737368e-13f;
+
+// Stride (floats) between the zero-padded LDS columns of lpp * epl rows: the one definition that the kernels index
+// with and that the host sizes their LDS from (jacobi_plan).
+//   16 lanes per column pair and more: + 2 (even: 8-byte aligned columns; PMC: no bank conflicts).
+//   4 lanes: a half-wave's ds_read_b64 touches 8 different columns, 8 banks each; with the stride 8 x odd the 8
+//     consecutive columns of a round-robin round tile the 64 banks exactly (PMC with + 2: 40 % of the LDS cycles were
+//     conflicts).  4 epl already 8 x odd -- the 196-row columns of cfg-4's cores, epl = 50: no padding at all, which is
+//     what lets a 196 x 196 matrix fit one CU's LDS.
+//   8 lanes: 4 columns of 16 banks per half-wave, stride 16 x odd.
+__host__ __device__ constexpr int jacobi_ld(int lpp, int epl) {
+    return lpp * epl + (lpp == 4 ? ((lpp * epl / 8) % 2 == 0 ? 8 : 0) : lpp == 8 ? 16 : 2);
+}
 
 struct Rot {
     float c, s, t; // fp32 cosine / sine / tangent of the plane rotation
@@ -186,13 +200,7 @@ __global__ void __launch_bounds__((LPP == 4 && EPL >= 48) ? 512 : 1024) jacobi_l
                                                            int rows_tot, int n_fixed, const int* __restrict__ n_arr,
                                                            int max_sweeps, float tol, float* __restrict__ colnorm,
                                                            int colnorm_stride, int* __restrict__ sweeps_out) {
-    // Column stride.  16 lanes per pair: + 2 (even: 8-byte aligned columns; PMC: no bank conflicts).  4 lanes per pair: a
-    // half-wave's ds_read_b64 touches 8 different columns, 8 banks each; with the stride 8 x odd the 8 consecutive
-    // columns of a round-robin round tile the 64 banks exactly (PMC with + 2: 40 % of the LDS cycles were conflicts).
-    // (8 lanes per pair: 4 columns of 16 banks per half-wave, stride 16 x odd.)
-    // (4 lanes per pair, 4 EPL already 8 x odd -- the 196-row columns of cfg-4's cores, EPL = 50: no padding at all, which
-    // is what lets a 196 x 196 matrix fit one CU's LDS)
-    constexpr int LD = LPP * EPL + (LPP == 4 ? (((LPP * EPL / 8) % 2 == 0) ? 8 : 0) : LPP == 8 ? 16 : 2);
+    constexpr int LD = jacobi_ld(LPP, EPL);
     static_assert(LPP != 4 || ((LD / 8) % 2 == 1 && LD % 8 == 0), "stride must come out as 8 x odd");
     static_assert(LPP != 8 || ((LPP * EPL / 16) % 2 == 0), "stride must come out as 16 x odd");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -333,7 +341,7 @@ __global__ void __launch_bounds__(512, 4) jacobi_oe_kernel(float* __restrict__ W
                                                            int colnorm_stride, int* __restrict__ sweeps_out) {
     static_assert(EPL % 2 == 0, "row chunks come in pairs");
     constexpr int H = EPL / 2;
-    constexpr int LD = 4 * EPL + (((4 * EPL / 8) % 2 == 0) ? 8 : 0);   // 8 x odd: see jacobi_lds_kernel
+    constexpr int LD = jacobi_ld(4, EPL);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int m = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
     const int n_even = (n + 1) & ~1, G = n_even / 2;
@@ -446,13 +454,13 @@ __global__ void __launch_bounds__(512, 4) jacobi_oe_kernel(float* __restrict__ W
 //           normalisation defects and the number of sweeps.
 //   pass 2, jacobi_apply_log_kernel: the riding rows in LDS, the log replayed on them -- no dot products, no
 //           reductions, the same rotations in the same order, so the result is what the one-kernel form computes.
-// 4 lanes per column pair; column stride LPP EPL (+ 8) = 8 x odd (see jacobi_lds_kernel).
+// 4 lanes per column pair; column stride LPP EPL (+ 8) = 8 x odd (see jacobi_ld).
 // Log entry of (sweep s, round r, pair seat t): ((s (n_even - 1) + r) n_even / 2 + t).
 // ---------------------------------------------------------------------------
 template <int EPL>
 struct TwoPassShape {
     static constexpr int LPP = 4;
-    static constexpr int LD = LPP * EPL + (((LPP * EPL / 8) % 2 == 0) ? 8 : 0);
+    static constexpr int LD = jacobi_ld(LPP, EPL);
     static_assert((LD / 8) % 2 == 1 && LD % 8 == 0, "stride must come out as 8 x odd");
 };
 
@@ -608,7 +616,8 @@ __global__ void __launch_bounds__(1024) jacobi_block_round_kernel(float* __restr
                                                                   int round, int sweep, int max_sweeps,
                                                                   float tol, int* __restrict__ flags,
                                                                   int* __restrict__ norm2_bits) {
-    constexpr int LD = LPP * EPL + 2;   // even: 8-byte aligned columns for the paired accesses
+    static_assert(LPP >= 16, "a panel pair is owned by one DPP row or more");
+    constexpr int LD = jacobi_ld(LPP, EPL);   // + 2, even: 8-byte aligned columns for the paired accesses
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int m = blockIdx.y;
     if (sweep > 0 && flags[m * max_sweeps + sweep - 1] == 0) return;  // converged in an earlier sweep
@@ -814,46 +823,281 @@ __global__ void __launch_bounds__(256) sort_extract_kernel(const float* __restri
 
 using namespace basd;
 
-
-extern "C" {
-
 // Largest LDS the resident solver may use (bytes); leaves room for the runtime.
 #define BASD_JACOBI_LDS_LIMIT (156 * 1024)
-
-int basd_jacobi_workspace_ints(int batch, int max_sweeps) { return 2 * batch * max_sweeps; }
-
 // Longest column (rows_dot, and riding rows) the block path of basd_jacobi_onesided has a panel shape for: 64 lanes
 // per column pair x 16 elements per lane.  Also the largest order of a plain square problem, per-matrix orders included.
 #define BASD_JACOBI_MAX_ROWS 1024
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// Host side.  jacobi_plan() decides which kernel shape solves a call; basd_jacobi_onesided launches what it decided,
+// and the "fits" queries that callers plan with are questions put to the same function.
+//
+// Every list of instantiated shapes stands here once, as a type: the planner picks an entry from it and the launcher
+// instantiates exactly its entries.
+// ---------------------------------------------------------------------------
+template <int... Vs>
+struct Ints {};
+
+// smallest entry >= need of an ascending list, 0 when there is none
+template <int... Vs>
+int first_at_least(Ints<Vs...>, int need) {
+    int sel = 0;
+    ((sel = (sel == 0 && Vs >= need) ? Vs : sel), ...);
+    return sel;
+}
+// f(std::integral_constant<int, V>) for every entry, in order / for the entry equal to v (false: v is not in the list)
+template <class F, int... Vs>
+void for_each_entry(Ints<Vs...>, F&& f) {
+    (f(std::integral_constant<int, Vs>{}), ...);
+}
+template <class F, int... Vs>
+bool with_entry(Ints<Vs...>, int v, F&& f) {
+    return ((Vs == v && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// elements per lane over the dot rows (stacked shapes: EPL = 2 DOT) ...
+using Stacked8Dot = Ints<2, 4, 6, 8>;          // jacobi_lds_kernel<2 D, D, 8>
+using Stacked4Dot = Ints<8, 12, 14, 16>;       // jacobi_lds_kernel<2 D, D, 4>
+// ... and over all rows of the plain shapes
+using Plain4Epl = Ints<8, 16, 24, 36, 50>;     // jacobi_oe_kernel<E>, jacobi_lds_kernel<E, E, 4>
+using Lds16Epl = Ints<2, 4, 6, 8, 12, 16, 20>; // jacobi_lds_kernel<E, E, 16>; stacked <E, E / 2, 16> for E % 4 == 0
+using TwoPassEpl = Ints<28, 36, 44, 50>;       // jacobi_top_logged_kernel<E>
+// block panels, jacobi_block_round_kernel<E, D, LPP>: D of the stacked shapes (E = 2 D), E = D of the plain ones
+using BlockLanes = Ints<64, 32, 16>;
+template <int LPP, bool STACKED> struct BlockDots;
+template <> struct BlockDots<64, true> : Ints<2, 4, 6, 8, 10, 12, 16> {};   // 10: stacked cores of 577..640 rows
+template <> struct BlockDots<64, false> : Ints<2, 4, 6, 8, 12, 16> {};
+template <> struct BlockDots<32, true> : Ints<4, 8, 12, 16, 20> {};
+template <> struct BlockDots<32, false> : Ints<4, 8, 12, 16, 20> {};
+template <> struct BlockDots<16, true> : Ints<8, 10, 14, 16, 20> {};
+template <> struct BlockDots<16, false> : Ints<8, 10, 14, 16, 20, 28, 32> {};
+
+enum JacobiRoute {      // in order of precedence; the values are those basd_jacobi_plan_query reports
+    kUnsupported = 0,
+    kStacked8 = 1,      // LDS-resident, stacked, 8 lanes per column pair
+    kStacked4 = 2,      // LDS-resident, stacked, 4 lanes
+    kPlain8 = 3,        // LDS-resident, plain, <20, 20, 8> (round-robin ordering only)
+    kOddEven = 4,       // register-resident, plain, odd-even ordering
+    kPlain4 = 5,        // LDS-resident, plain, 4 lanes
+    kLds16 = 6,         // LDS-resident, 16 lanes: stacked, plain and per-matrix orders
+    kBlock = 7,         // block rounds through L2 / HBM
+    kTwoPass = 8        // basd_jacobi_stacked_twopass (its own entry point, never chosen by jacobi_plan)
+};
+
+struct JacobiPlan {
+    int route;
+    int lpp, epl, dot;  // lanes per column pair, elements per lane over all rows / over the dot rows
+    int threads;
+    size_t lds;         // dynamic LDS bytes of a launch
+    int bw, nblk;       // block route: columns per block, blocks (even)
+};
+const JacobiPlan kNoPlan{kUnsupported, 0, 0, 0, 0, 0, 0, 0};
+
+inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+inline int max_of(int a, int b) { return a > b ? a : b; }
+
+// One workgroup per matrix with `cols` padded columns (+ a cached norm and a defect each) in LDS and `pairs` column
+// pairs per round: all of them in flight at once when that fits the block.  epl == 0 (no list entry) or too much LDS:
+// no plan.
+JacobiPlan one_workgroup_plan(int route, int lpp, int epl, int dot, int cols, int pairs) {
+    if (!epl) return kNoPlan;
+    JacobiPlan p{route, lpp, epl, dot, ceil_div(pairs * lpp, 64) * 64, 0, 0, 0};
+    if (p.threads > 1024) p.threads = 1024;
+    p.lds = (size_t)cols * (jacobi_ld(lpp, epl) + 2) * sizeof(float);
+    return p.lds <= BASD_JACOBI_LDS_LIMIT ? p : kNoPlan;
+}
+
+// Panel shape of the block route: lanes per column pair (64 / 32 / 16), elements per lane, columns per block.  A sweep
+// is nblk - 1 trips of the whole matrix through L2 / HBM, so: the widest panel that fits LDS; ties go to more lanes per
+// pair.  No plan: columns too long for a two-column panel in LDS.
+JacobiPlan block_plan(int rows_dot, int rows_tot, int n) {
+    const bool stacked = rows_tot > rows_dot;
+    JacobiPlan best = kNoPlan;
+    best.nblk = 1 << 30;
+    for_each_entry(BlockLanes{}, [&](auto l) {
+        constexpr int lpp = l;
+        const int cd = ceil_div(rows_dot, 2 * lpp), cr = ceil_div(rows_tot - rows_dot, 2 * lpp);
+        const int need = 2 * (stacked && cr > cd ? cr : cd);
+        const int sel = stacked ? first_at_least(BlockDots<lpp, true>{}, need) : first_at_least(BlockDots<lpp, false>{}, need);
+        if (!sel) return;
+        const int epl = stacked ? 2 * sel : sel;
+        const size_t col_bytes = sizeof(float) * (size_t)jacobi_ld(lpp, epl);
+        int bw = (int)((BASD_JACOBI_LDS_LIMIT - 64) / (2 * (col_bytes + 8)));      // + norm / defect per column
+        if (bw > 1024 / lpp) bw = 1024 / lpp;
+        if (bw > ((n + 1) & ~1)) bw = (n + 1) & ~1;
+        bw &= ~1;
+        if (bw < 2) return;
+        const int nb = (ceil_div(n, bw) + 1) & ~1;
+        if (nb < best.nblk)
+            best = JacobiPlan{kBlock, lpp, epl, sel, lpp * bw, (size_t)2 * bw * (jacobi_ld(lpp, epl) + 2) * sizeof(float), bw, nb};
+    });
+    return best.route == kBlock ? best : kNoPlan;
+}
+
+// Which kernel shape solves `batch` matrices of rows_tot x n (the first rows_dot rows orthogonalised), in order of
+// precedence; a route whose shape does not fit falls through to the next.  Pure: no HIP call, no global state --
+// forced_lanes / ordering are the values of basd_jacobi_tuning / basd_jacobi_ordering.
+// Thresholds measured on MI355X, stacked: 1024 x (98 x 49): 0.87 ms with 16 lanes per pair, 0.80 with 8, 0.70 with 4;
+// 512 x (72 x 36): 0.45 / 0.36 / 0.41.
+JacobiPlan jacobi_plan(int rows_dot, int rows_tot, int n, int batch, bool per_matrix_orders, int forced_lanes,
+                       int ordering) {
+    const int n_even = (n + 1) & ~1, pairs = n_even / 2, ride = rows_tot - rows_dot;
+    const bool stacked = ride > 0;
+    const bool plain = !stacked && !per_matrix_orders;          // per-matrix orders: 16-lane and block routes only
+    int lanes = forced_lanes;                                   // automatic choice: large batches of stacked matrices
+    if (lanes == 0 && stacked && batch >= 256) lanes = n_even >= 40 ? 4 : (n_even >= 16 ? 8 : 16);
+    JacobiPlan p = kNoPlan;
+
+    if (stacked && n_even >= 8 && lanes == 8) {                 // halves in 16-row chunks, DOT = 2 chunks
+        const int dot = first_at_least(Stacked8Dot{}, 2 * max_of(ceil_div(rows_dot, 16), ceil_div(ride, 16)));
+        p = one_workgroup_plan(kStacked8, 8, 2 * dot, dot, n_even, pairs);
+        if (p.route) return p;
+    }
+    // throughput shape: large batches of small stacked matrices
+    if (stacked && n_even >= 8 && lanes == 4) {                 // halves in 8-row chunks, DOT = 2 chunks
+        const int dot = first_at_least(Stacked4Dot{}, 2 * max_of(ceil_div(rows_dot, 8), ceil_div(ride, 8)));
+        p = one_workgroup_plan(kStacked4, 4, 2 * dot, dot, n_even, pairs);
+        if (p.route) return p;
+    }
+    // (round-robin ordering only) long columns at about one matrix per CU (cfg-5: 256 cores of 144 x 144): what counts
+    // there is the latency of one round, and half the elements per lane shorten it.  The odd-even solver beats it there
+    // as well (cfg-5: 6.54 -> 5.9 ms per step)
+    if (ordering == 0 && plain && rows_tot > 96 && rows_tot <= 160 && n_even <= 160 &&
+        (lanes == 8 || (lanes == 0 && batch >= 128 && batch <= 320))) {
+        p = one_workgroup_plan(kPlain8, 8, 20, 20, n_even, pairs);
+        if (p.route) return p;
+    }
+    // plain matrices in batches (the transposed Procrustes cores: no riding rows, rows_tot == rows_dot), 4 lanes per pair
+    const int e4 = first_at_least(Plain4Epl{}, ceil_div(rows_tot, 4));
+    if (ordering == 1 && plain && n_even >= 8 && (lanes == 0 || lanes == 4) &&
+        (forced_lanes == 4 || (batch >= 128 && n_even >= 40) || n_even >= 96)) {
+        p = one_workgroup_plan(kOddEven, 4, e4, e4, pairs + 1, pairs);      // a mail slot per even seat, and one more
+        if (p.route && p.threads <= 512) return p;                          // one lane group per pair: no loop over pairs
+    }
+    if (plain && n_even >= 8 && (lanes == 4 || (lanes == 0 && batch >= 128 && n_even >= 40))) {
+        p = one_workgroup_plan(kPlain4, 4, e4, e4, n_even, pairs);
+        if (p.route) return p;
+    }
+    // the whole (padded) matrix in one CU, one DPP row per pair; stacked: EPL = 2 DOT with DOT even
+    const int chunks = max_of(ceil_div(rows_dot, 16), ceil_div(ride, 16));
+    const int e16 = first_at_least(Lds16Epl{}, stacked ? (2 * chunks + 3) & ~3 : chunks);
+    p = one_workgroup_plan(kLds16, 16, e16, stacked ? e16 / 2 : e16, n_even, pairs);
+    if (p.route) return p;
+    return block_plan(rows_dot, rows_tot, n);
+}
+
+// pass 1 of the two-pass solver for 2n x n cores: the top n x n in LDS, 4 lanes per pair, one lane group per pair
+JacobiPlan twopass_plan(int n) {
+    const int n_even = (n + 1) & ~1;
+    return one_workgroup_plan(kTwoPass, 4, first_at_least(TwoPassEpl{}, ceil_div(n, 4)), 0, n_even, n_even / 2);
+}
+int twopass_epl(int n) { return twopass_plan(n).epl; }      // 0: n > 196
+// the one-kernel 16-lane LDS solver of basd_jacobi_onesided takes a 2n x n core
+bool stacked_lds_fits(int n) { return jacobi_plan(n, 2 * n, n, 1, false, 16, 1).route == kLds16; }
+
+// ---- launches: one function per kernel family ----
+struct JacobiArgs {
+    float* W;
+    long batch_stride;
+    int rows_dot, rows_tot, n, batch;
+    const int* n_arr;
+    float* colnorm;
+    int colnorm_stride, max_sweeps;
+    float tol;
+    int* flags;
+    int* sweeps_out;
+    hipStream_t stream;
+};
+
+void allow_lds(const void* kernel, size_t lds, bool always = false) {
+    if (always || lds > 48 * 1024)
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BASD_JACOBI_LDS_LIMIT);
+}
+
+template <int E, int D, int L>
+void launch_lds(const JacobiPlan& p, const JacobiArgs& a, bool always_allow = false) {
+    allow_lds((const void*)jacobi_lds_kernel<E, D, L>, p.lds, always_allow);
+    jacobi_lds_kernel<E, D, L><<<a.batch, p.threads, p.lds, a.stream>>>(a.W, a.batch_stride, a.rows_dot, a.rows_tot, a.n,
+                                                                       a.n_arr, a.max_sweeps, a.tol, a.colnorm,
+                                                                       a.colnorm_stride, a.sweeps_out);
+}
+
+template <int E>
+void launch_odd_even(const JacobiPlan& p, const JacobiArgs& a) {
+    allow_lds((const void*)jacobi_oe_kernel<E>, p.lds);
+    jacobi_oe_kernel<E><<<a.batch, p.threads, p.lds, a.stream>>>(a.W, a.batch_stride, a.rows_tot, a.n, a.max_sweeps, a.tol,
+                                                                a.colnorm, a.colnorm_stride, a.sweeps_out);
+}
+
+// one launch per round-robin round over blocks of p.bw columns, for every sweep that may be needed
+template <int E, int D, int L>
+void launch_block_rounds(const JacobiPlan& p, const JacobiArgs& a) {
+    allow_lds((const void*)jacobi_block_round_kernel<E, D, L>, p.lds);
+    for (int s = 0; s < a.max_sweeps; ++s)
+        for (int r = 0; r < p.nblk - 1; ++r)
+            jacobi_block_round_kernel<E, D, L><<<dim3(p.nblk / 2, a.batch), p.threads, p.lds, a.stream>>>(
+                a.W, a.batch_stride, a.rows_dot, a.rows_tot, a.n, a.n_arr, p.nblk, p.bw, r, s, a.max_sweeps, a.tol, a.flags,
+                a.flags + (size_t)a.batch * a.max_sweeps);
+}
+
+int run_block_route(const JacobiPlan& p, const JacobiArgs& a) {
+    const bool stacked = a.rows_tot > a.rows_dot;
+    hipError_t err = hipMemsetAsync(a.flags, 0, sizeof(int) * (size_t)2 * a.batch * a.max_sweeps, a.stream);
+    if (err != hipSuccess) return (int)err;
+    with_entry(BlockLanes{}, p.lpp, [&](auto l) {
+        constexpr int L = l;
+        if (stacked)
+            with_entry(BlockDots<L, true>{}, p.dot, [&](auto d) { constexpr int D = d; launch_block_rounds<2 * D, D, L>(p, a); });
+        else
+            with_entry(BlockDots<L, false>{}, p.dot, [&](auto d) { constexpr int D = d; launch_block_rounds<D, D, L>(p, a); });
+    });
+    if (a.sweeps_out)
+        block_sweeps_kernel<<<(a.batch + 255) / 256, 256, 0, a.stream>>>(a.flags, a.batch, a.max_sweeps, a.sweeps_out);
+    colnorm_kernel<<<dim3((a.n + 3) / 4, a.batch), 256, 0, a.stream>>>(a.W, a.batch_stride, a.rows_dot, a.rows_tot, a.n, a.n_arr,
+                                                                       a.colnorm, a.colnorm_stride);
+    BASD_RETURN_LAST();
+}
+
+// pass 2 of the two-pass solver: the riding rows in chunks of 4 C rows
+template <int C>
+void launch_apply_log(const JacobiPlan& p, float* W, long batch_stride, int n, int batch, const f32x2* rotlog, long entries,
+                      const float* dev, const int* sweeps, hipStream_t stream) {
+    const size_t lds = sizeof(float) * (size_t)((n + 1) & ~1) * TwoPassShape<C>::LD;
+    jacobi_apply_log_kernel<C><<<dim3(batch, ceil_div(n, 4 * C)), p.threads, lds, stream>>>(W, batch_stride, 2 * n, n, n, rotlog,
+                                                                                          entries, dev, sweeps);
+}
+
+// Test / tuning hooks, process-wide: see basd_jacobi_tuning / basd_jacobi_ordering
+int g_jacobi_lanes = 0;
+int g_jacobi_ordering = 1;
+
+}  // namespace
+
+extern "C" {
+
+int basd_jacobi_workspace_ints(int batch, int max_sweeps) { return 2 * batch * max_sweeps; }
+
 int basd_jacobi_max_rows(void) { return BASD_JACOBI_MAX_ROWS; }
 
-// 1 when basd_jacobi_onesided solves a batch (>= 128) of plain n x n matrices in LDS with 4 lanes per column pair
-// (orders 40..144): the transposed Procrustes cores then need no riding rows (basd_procrustes_forward_fused).
-// column stride (floats) of the plain 4-lane solver for e elements per lane: 4 e, + 8 unless that is 8 x odd already
-static inline size_t plain4_ld(int e) { return 4 * (size_t)e + (((4 * e / 8) % 2 == 0) ? 8 : 0); }
+// 1 when the plain 4-lane LDS shape (jacobi_lds_kernel<E, E, 4>) fits order n and n is one of the orders (n_even >= 40)
+// that basd_jacobi_onesided gives it, or the odd-even solver, for batches >= 128 without a tuning hook.  It is the
+// planner's answer for a call with 4 lanes forced and the round-robin ordering: the batch and the 512-thread cap of
+// the odd-even kernel play no part, callers test batch >= 128 themselves.  The transposed Procrustes cores then need
+// no riding rows (basd_procrustes_forward_fused).
 int basd_jacobi_plain4_fits(int n) {
-    const int n_even = (n + 1) & ~1;
-    if (n_even < 40 || n > 200) return 0;
-    static const int p_epl[] = {8, 16, 24, 36, 50};
-    for (int e : p_epl)
-        if (4 * e >= n) return (size_t)n_even * (plain4_ld(e) + 2) * sizeof(float) <= BASD_JACOBI_LDS_LIMIT;
-    return 0;
+    return ((n + 1) & ~1) >= 40 && jacobi_plan(n, n, n, 128, false, 4, 0).route == kPlain4;
 }
 
 // 1 when basd_jacobi_onesided keeps square matrices of order n in LDS with 16 lanes per column pair and solves them in
-// one launch: the form basd_selector_chain_tail queues speculatively for its principal-angle matrices.
-int basd_jacobi_lds_square_fits(int n) {
-    if (n < 1) return 0;
-    const int n_even = (n + 1) & ~1, epl = (n + 15) / 16;
-    static const int lds_epl[] = {2, 4, 6, 8, 12, 16, 20};
-    for (int e : lds_epl)
-        if (e >= epl) return (size_t)n_even * (16 * e + 4) * sizeof(float) <= BASD_JACOBI_LDS_LIMIT;
-    return 0;
-}
+// one launch: the form basd_selector_chain_tail queues speculatively for its principal-angle matrices (per-matrix
+// orders, which reach no other LDS route).
+int basd_jacobi_lds_square_fits(int n) { return n >= 1 && jacobi_plan(n, n, n, 1, true, 0, 1).route == kLds16; }
 
 // Test / tuning hook: lanes per column pair of the LDS-resident solver -- 0 = automatic, 4 / 8 / 16 = forced where the
 // shape allows (4 and 8: stacked matrices only).  Process-wide.
-static int g_jacobi_lanes = 0;
 int basd_jacobi_tuning(int lanes_per_pair) {
     if (lanes_per_pair != 0 && lanes_per_pair != 4 && lanes_per_pair != 8 && lanes_per_pair != 16) return BASD_EINVAL;
     g_jacobi_lanes = lanes_per_pair;
@@ -862,10 +1106,22 @@ int basd_jacobi_tuning(int lanes_per_pair) {
 
 // Test / tuning hook: ordering of the plain batched solver -- 1 (default) = odd-even, columns in registers
 // (jacobi_oe_kernel); 0 = round-robin through LDS (jacobi_lds_kernel<E, E, 4>).  Process-wide.
-static int g_jacobi_ordering = 1;
 int basd_jacobi_ordering(int odd_even) {
     if (odd_even != 0 && odd_even != 1) return BASD_EINVAL;
     g_jacobi_ordering = odd_even;
+    return BASD_OK;
+}
+
+// What basd_jacobi_onesided would launch for this shape under the current tuning hooks; no HIP call.
+//   out8: route (JacobiRoute: 1..7 in order of precedence, 0 = no kernel shape), lanes per column pair, elements per
+//   lane, of which over the dot rows, threads per workgroup, dynamic LDS bytes, and for the block route columns per
+//   block and number of blocks.
+int basd_jacobi_plan_query(int rows_dot, int rows_tot, int n, int batch, int per_matrix_orders, int* out8) {
+    BASD_CHECK_ARG(out8 && rows_dot > 0 && rows_tot >= rows_dot && n > 0 && batch > 0);
+    BASD_CHECK_ARG(!(rows_tot > rows_dot && per_matrix_orders));
+    const JacobiPlan p = jacobi_plan(rows_dot, rows_tot, n, batch, per_matrix_orders != 0, g_jacobi_lanes, g_jacobi_ordering);
+    const int out[8] = {p.route, p.lpp, p.epl, p.dot, p.threads, (int)p.lds, p.bw, p.nblk};
+    for (int i = 0; i < 8; ++i) out8[i] = out[i];
     return BASD_OK;
 }
 
@@ -885,313 +1141,42 @@ int basd_jacobi_onesided(float* W, long batch_stride, int rows_dot, int rows_tot
     BASD_CHECK_ARG(W && colnorm && rows_dot > 0 && rows_tot >= rows_dot && n > 0 && batch > 0 && max_sweeps > 0);
     // a pair counts as orthogonal when |cos| <= tol; <= 0 selects the round-off level eps * sqrt(rows)
     const float tol = tol_cos > 0.f ? tol_cos : 1.2e-7f * sqrtf((float)rows_dot);
-    const int n_even = (n + 1) & ~1;
-    // per-lane element counts of the zero-padded LDS columns (16 lanes per column pair)
     const bool stacked = rows_tot > rows_dot;
-    const int dot16 = (rows_dot + 15) / 16, ride16 = (rows_tot - rows_dot + 15) / 16;
-    const int half = dot16 > ride16 ? dot16 : ride16;          // stacked layouts: EPL = 2 * DOT
-    const int epl = stacked ? 2 * half : dot16;
     BASD_CHECK_ARG(!(stacked && n_arr));
-
-    // ---- LDS-resident, 8 lanes per column pair (stacked matrices) ----
-    // automatic choice for large batches of stacked matrices (measured on MI355X, 1024 x (98 x 49): 0.87 ms with 16 lanes
-    // per pair, 0.80 with 8, 0.70 with 4; 512 x (72 x 36): 0.45 / 0.36 / 0.41)
-    int lanes = g_jacobi_lanes;
-    if (lanes == 0 && stacked && batch >= 256) lanes = n_even >= 40 ? 4 : (n_even >= 16 ? 8 : 16);
-    if (stacked && n_even >= 8 && lanes == 8) {
-        const int dot16 = (rows_dot + 15) / 16, ride16 = (rows_tot - rows_dot + 15) / 16;
-        const int half16 = dot16 > ride16 ? dot16 : ride16;       // 16-row chunks per half; DOT = 2 * half16
-        const int d8 = 2 * half16;
-        const size_t lds8 = (size_t)n_even * (8 * 2 * d8 + 16 + 2) * sizeof(float);
-        if (d8 <= 8 && lds8 <= BASD_JACOBI_LDS_LIMIT) {
-            int threads = (((n_even / 2) * 8 + 63) / 64) * 64;
-            if (threads > 1024) threads = 1024;
-#define LAUNCH_LDS8(D)                                                                                               \
-    do {                                                                                                             \
-        if (lds8 > 48 * 1024)                                                                                        \
-            (void)hipFuncSetAttribute((const void*)jacobi_lds_kernel<2 * (D), D, 8>,                                 \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BASD_JACOBI_LDS_LIMIT);            \
-        jacobi_lds_kernel<2 * (D), D, 8><<<batch, threads, lds8, stream>>>(W, batch_stride, rows_dot, rows_tot, n,   \
-                                                                           n_arr, max_sweeps, tol, colnorm,          \
-                                                                           colnorm_stride, sweeps_out);              \
-    } while (0)
-            switch (d8) {
-                case 2: LAUNCH_LDS8(2); break;
-                case 4: LAUNCH_LDS8(4); break;
-                case 6: LAUNCH_LDS8(6); break;
-                default: LAUNCH_LDS8(8); break;
-            }
-#undef LAUNCH_LDS8
-            BASD_RETURN_LAST();
-        }
+    const JacobiPlan p = jacobi_plan(rows_dot, rows_tot, n, batch, n_arr != nullptr, g_jacobi_lanes, g_jacobi_ordering);
+    const JacobiArgs a{W, batch_stride, rows_dot, rows_tot, n, batch, n_arr, colnorm, colnorm_stride, max_sweeps, tol,
+                       flags, sweeps_out, stream};
+    switch (p.route) {
+        case kStacked8:
+            with_entry(Stacked8Dot{}, p.dot, [&](auto d) { constexpr int D = d; launch_lds<2 * D, D, 8>(p, a); });
+            break;
+        case kStacked4:
+            with_entry(Stacked4Dot{}, p.dot, [&](auto d) { constexpr int D = d; launch_lds<2 * D, D, 4>(p, a); });
+            break;
+        case kPlain8:
+            launch_lds<20, 20, 8>(p, a, true);      // the one route that raises the LDS limit whatever it needs
+            break;
+        case kOddEven:
+            with_entry(Plain4Epl{}, p.epl, [&](auto e) { constexpr int E = e; launch_odd_even<E>(p, a); });
+            break;
+        case kPlain4:
+            with_entry(Plain4Epl{}, p.epl, [&](auto e) { constexpr int E = e; launch_lds<E, E, 4>(p, a); });
+            break;
+        case kLds16:
+            with_entry(Lds16Epl{}, p.epl, [&](auto e) {
+                constexpr int E = e;
+                if (!stacked) launch_lds<E, E, 16>(p, a);
+                else if constexpr (E % 4 == 0) launch_lds<E, E / 2, 16>(p, a);
+            });
+            break;
+        default:                                     // the block route is the only one that needs `flags`
+            BASD_CHECK_ARG(flags != nullptr);
+            return p.route == kBlock ? run_block_route(p, a) : BASD_EUNSUPPORTED;
     }
-
-    // ---- LDS-resident, throughput shape: large batches of small stacked matrices, 4 lanes per column pair ----
-    if (stacked && n_even >= 8 && lanes == 4) {
-        const int dot8 = (rows_dot + 7) / 8, ride8 = (rows_tot - rows_dot + 7) / 8;
-        const int half8 = dot8 > ride8 ? dot8 : ride8;            // 8-row chunks per half; DOT = 2 * half8 elements / lane
-        static const int q_dot[] = {8, 12, 14, 16};
-        int d4 = 0;
-        for (int dq : q_dot)
-            if (dq >= 2 * half8) { d4 = dq; break; }
-        const size_t lds4 = (size_t)n_even * (4 * 2 * d4 + 8 + 2) * sizeof(float);
-        if (d4 && lds4 <= BASD_JACOBI_LDS_LIMIT) {
-            int threads = (((n_even / 2) * 4 + 63) / 64) * 64;
-            if (threads > 1024) threads = 1024;
-#define LAUNCH_LDS4(D)                                                                                               \
-    do {                                                                                                             \
-        if (lds4 > 48 * 1024)                                                                                        \
-            (void)hipFuncSetAttribute((const void*)jacobi_lds_kernel<2 * (D), D, 4>,                                 \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BASD_JACOBI_LDS_LIMIT);            \
-        jacobi_lds_kernel<2 * (D), D, 4><<<batch, threads, lds4, stream>>>(W, batch_stride, rows_dot, rows_tot, n,   \
-                                                                           n_arr, max_sweeps, tol, colnorm,          \
-                                                                           colnorm_stride, sweeps_out);              \
-    } while (0)
-            switch (d4) {
-                case 8: LAUNCH_LDS4(8); break;
-                case 12: LAUNCH_LDS4(12); break;
-                case 14: LAUNCH_LDS4(14); break;
-                default: LAUNCH_LDS4(16); break;
-            }
-#undef LAUNCH_LDS4
-            BASD_RETURN_LAST();
-        }
-    }
-
-    // ---- (round-robin ordering only) the same with 8 lanes per pair for long columns at about one matrix per CU (cfg-5:
-    // 256 cores of 144 x 144): what counts there is the latency of one round, and half the elements per lane shorten it.
-    // The odd-even solver below beats it there as well (cfg-5: 6.54 -> 5.9 ms per step) ----
-    if (g_jacobi_ordering == 0 && !stacked && !n_arr && rows_tot > 96 && rows_tot <= 160 && n_even <= 160 &&
-        (lanes == 8 || (lanes == 0 && batch >= 128 && batch <= 320))) {
-        const size_t lds8p = (size_t)n_even * (8 * 20 + 16 + 2) * sizeof(float);
-        if (lds8p <= BASD_JACOBI_LDS_LIMIT) {
-            int threads = (((n_even / 2) * 8 + 63) / 64) * 64;
-            if (threads > 1024) threads = 1024;
-            (void)hipFuncSetAttribute((const void*)jacobi_lds_kernel<20, 20, 8>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BASD_JACOBI_LDS_LIMIT);
-            jacobi_lds_kernel<20, 20, 8><<<batch, threads, lds8p, stream>>>(W, batch_stride, rows_dot, rows_tot, n, n_arr,
-                                                                            max_sweeps, tol, colnorm, colnorm_stride,
-                                                                            sweeps_out);
-            BASD_RETURN_LAST();
-        }
-    }
-
-    // ---- register-resident, odd-even ordering: plain matrices in batches (the transposed Procrustes cores) ----
-    if (g_jacobi_ordering == 1 && !stacked && !n_arr && n_even >= 8 && rows_tot == rows_dot &&
-        (lanes == 0 || lanes == 4) && (g_jacobi_lanes == 4 || (batch >= 128 && n_even >= 40) || n_even >= 96)) {
-        static const int o_epl[] = {8, 16, 24, 36, 50};
-        int e4 = 0;
-        for (int e : o_epl)
-            if (4 * e >= rows_tot) { e4 = e; break; }
-        const int G = n_even / 2;
-        const size_t lds_oe = (size_t)(G + 1) * (plain4_ld(e4) + 2) * sizeof(float);
-        const int threads = ((G * 4 + 63) / 64) * 64;
-        if (e4 && threads <= 512 && lds_oe <= BASD_JACOBI_LDS_LIMIT) {
-#define LAUNCH_OE(E)                                                                                                  \
-    do {                                                                                                              \
-        if (lds_oe > 48 * 1024)                                                                                       \
-            (void)hipFuncSetAttribute((const void*)jacobi_oe_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                      BASD_JACOBI_LDS_LIMIT);                                                         \
-        jacobi_oe_kernel<E><<<batch, threads, lds_oe, stream>>>(W, batch_stride, rows_tot, n, max_sweeps, tol, colnorm, \
-                                                                colnorm_stride, sweeps_out);                          \
-    } while (0)
-            switch (e4) {
-                case 8: LAUNCH_OE(8); break;
-                case 16: LAUNCH_OE(16); break;
-                case 24: LAUNCH_OE(24); break;
-                case 36: LAUNCH_OE(36); break;
-                default: LAUNCH_OE(50); break;
-            }
-#undef LAUNCH_OE
-            BASD_RETURN_LAST();
-        }
-    }
-
-    // ---- LDS-resident, plain square-ish matrices in large batches (the transposed Procrustes cores: no riding rows),
-    // 4 lanes per column pair.  Elements per lane: multiples of 4 (column stride 4 EPL + 8 = 8 x odd). ----
-    if (!stacked && !n_arr && n_even >= 8 && (lanes == 4 || (lanes == 0 && batch >= 128 && n_even >= 40))) {
-        static const int p_epl[] = {8, 16, 24, 36, 50};
-        int e4 = 0;
-        for (int e : p_epl)
-            if (4 * e >= rows_tot) { e4 = e; break; }
-        const size_t lds4 = (size_t)n_even * (plain4_ld(e4) + 2) * sizeof(float);
-        if (e4 && lds4 <= BASD_JACOBI_LDS_LIMIT) {
-            int threads = (((n_even / 2) * 4 + 63) / 64) * 64;
-            if (threads > 1024) threads = 1024;
-#define LAUNCH_P4(E)                                                                                                  \
-    do {                                                                                                              \
-        if (lds4 > 48 * 1024)                                                                                         \
-            (void)hipFuncSetAttribute((const void*)jacobi_lds_kernel<E, E, 4>,                                        \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BASD_JACOBI_LDS_LIMIT);             \
-        jacobi_lds_kernel<E, E, 4><<<batch, threads, lds4, stream>>>(W, batch_stride, rows_dot, rows_tot, n, n_arr,   \
-                                                                     max_sweeps, tol, colnorm, colnorm_stride,        \
-                                                                     sweeps_out);                                     \
-    } while (0)
-            switch (e4) {
-                case 8: LAUNCH_P4(8); break;
-                case 16: LAUNCH_P4(16); break;
-                case 24: LAUNCH_P4(24); break;
-                case 36: LAUNCH_P4(36); break;
-                default: LAUNCH_P4(50); break;
-            }
-#undef LAUNCH_P4
-            BASD_RETURN_LAST();
-        }
-    }
-
-    // ---- LDS-resident: the whole (padded) matrix in one CU ----
-    static const int lds_epl[] = {2, 4, 6, 8, 12, 16, 20};
-    int e_lds = 0;
-    for (int e : lds_epl)
-        if (e >= epl && (!stacked || e % 4 == 0)) { e_lds = e; break; }
-    if (e_lds && (size_t)n_even * (16 * e_lds + 4) * sizeof(float) <= BASD_JACOBI_LDS_LIMIT) {
-        const size_t lds_bytes = (size_t)n_even * (16 * e_lds + 4) * sizeof(float);
-        // every pair of a round-robin round in flight at once when it fits the block
-        int threads = (((n_even / 2) * 16 + 63) / 64) * 64;
-        if (threads > 1024) threads = 1024;
-#define LAUNCH_LDS(E, D)                                                                                          \
-    do {                                                                                                          \
-        if (lds_bytes > 48 * 1024)                                                                                \
-            (void)hipFuncSetAttribute((const void*)jacobi_lds_kernel<E, D>,                                       \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BASD_JACOBI_LDS_LIMIT);         \
-        jacobi_lds_kernel<E, D><<<batch, threads, lds_bytes, stream>>>(W, batch_stride, rows_dot, rows_tot, n,    \
-                                                                        n_arr, max_sweeps, tol, colnorm,           \
-                                                                        colnorm_stride, sweeps_out);               \
-    } while (0)
-#define LAUNCH_LDS_E(E)                                      \
-    do {                                                     \
-        if (stacked) {                                       \
-            if constexpr ((E) % 4 == 0) LAUNCH_LDS(E, (E) / 2); \
-        } else {                                             \
-            LAUNCH_LDS(E, E);                                \
-        }                                                    \
-    } while (0)
-        switch (e_lds) {
-            case 2: LAUNCH_LDS_E(2); break;
-            case 4: LAUNCH_LDS_E(4); break;
-            case 6: LAUNCH_LDS_E(6); break;
-            case 8: LAUNCH_LDS_E(8); break;
-            case 12: LAUNCH_LDS_E(12); break;
-            case 16: LAUNCH_LDS_E(16); break;
-            default: LAUNCH_LDS_E(20); break;
-        }
-#undef LAUNCH_LDS_E
-#undef LAUNCH_LDS
-        BASD_RETURN_LAST();
-    }
-
-    // ---- block path: one launch per round-robin round over blocks of BW columns ----
-    BASD_CHECK_ARG(flags != nullptr);
-    // Panel shape: lanes per column pair (64 / 32 / 16), elements per lane, columns per block.  A sweep is nblk - 1
-    // trips of the whole matrix through L2 / HBM, so: the widest panel that fits LDS; ties go to more lanes per pair.
-    struct Shape { int lpp, epl, dot, bw, nblk; };
-    Shape best{0, 0, 0, 0, 1 << 30};
-    // instantiated element counts per lane: `dot` of the stacked shapes (EPL = 2 dot), EPL of the plain ones
-    static const int st64[] = {2, 4, 6, 8, 10, 12, 16, 0}, pl64[] = {2, 4, 6, 8, 12, 16, 0};
-    static const int st32[] = {4, 8, 12, 16, 20, 0}, pl32[] = {4, 8, 12, 16, 20, 0};
-    static const int st16[] = {8, 10, 14, 16, 20, 0}, pl16[] = {8, 10, 14, 16, 20, 28, 32, 0};
-    static const int lpps[] = {64, 32, 16};
-    for (int lpp : lpps) {
-        const int cd = (rows_dot + 2 * lpp - 1) / (2 * lpp), cr = (rows_tot - rows_dot + 2 * lpp - 1) / (2 * lpp);
-        const int need = 2 * (stacked && cr > cd ? cr : cd);
-        const int* q = lpp == 64 ? (stacked ? st64 : pl64) : lpp == 32 ? (stacked ? st32 : pl32) : (stacked ? st16 : pl16);
-        int sel = 0;
-        for (; *q; ++q)
-            if (*q >= need) { sel = *q; break; }
-        if (!sel) continue;
-        const int epl = stacked ? 2 * sel : sel;
-        const size_t col_bytes = sizeof(float) * (size_t)(lpp * epl + 2);
-        int bw = (int)((BASD_JACOBI_LDS_LIMIT - 64) / (2 * (col_bytes + 8)));      // + norm / defect per column
-        if (bw > 1024 / lpp) bw = 1024 / lpp;
-        if (bw > ((n + 1) & ~1)) bw = (n + 1) & ~1;
-        bw &= ~1;
-        if (bw < 2) continue;
-        int nb = (n + bw - 1) / bw;
-        nb = (nb + 1) & ~1;
-        if (nb < best.nblk) best = Shape{lpp, epl, sel, bw, nb};
-    }
-    if (!best.lpp) return BASD_EUNSUPPORTED;                     // columns too long for a two-column panel in LDS
-    const int BW = best.bw, nblk = best.nblk;
-    const size_t panel_bytes = (size_t)2 * BW * (best.lpp * best.epl + 2 + 2) * sizeof(float);
-    hipError_t err = hipMemsetAsync(flags, 0, sizeof(int) * (size_t)2 * batch * max_sweeps, stream);
-    if (err != hipSuccess) return (int)err;
-#define LAUNCH_BLOCK(E, D, LP)                                                                                   \
-    do {                                                                                                         \
-        if (panel_bytes > 48 * 1024)                                                                             \
-            (void)hipFuncSetAttribute((const void*)jacobi_block_round_kernel<E, D, LP>,                          \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BASD_JACOBI_LDS_LIMIT);        \
-        for (int s = 0; s < max_sweeps; ++s)                                                                     \
-            for (int r = 0; r < nblk - 1; ++r)                                                                   \
-                jacobi_block_round_kernel<E, D, LP><<<dim3(nblk / 2, batch), LP * BW, panel_bytes, stream>>>(    \
-                    W, batch_stride, rows_dot, rows_tot, n, n_arr, nblk, BW, r, s, max_sweeps, tol, flags,       \
-                    flags + (size_t)batch * max_sweeps);                                                         \
-    } while (0)
-#define LAUNCH_BLOCK_SEL(Q, LP)                      \
-    do {                                             \
-        if (stacked) LAUNCH_BLOCK(2 * (Q), Q, LP);   \
-        else LAUNCH_BLOCK(Q, Q, LP);                 \
-    } while (0)
-    bool launched = true;
-    if (best.lpp == 64) {
-        switch (best.dot) {
-            case 2: LAUNCH_BLOCK_SEL(2, 64); break;
-            case 4: LAUNCH_BLOCK_SEL(4, 64); break;
-            case 6: LAUNCH_BLOCK_SEL(6, 64); break;
-            case 8: LAUNCH_BLOCK_SEL(8, 64); break;
-            case 10: LAUNCH_BLOCK(20, 10, 64); break;      // stacked cores of 577..640 rows (576 tokens)
-            case 12: LAUNCH_BLOCK_SEL(12, 64); break;
-            case 16: LAUNCH_BLOCK_SEL(16, 64); break;
-            default: launched = false; break;
-        }
-    } else if (best.lpp == 32) {
-        switch (best.dot) {
-            case 4: LAUNCH_BLOCK_SEL(4, 32); break;
-            case 8: LAUNCH_BLOCK_SEL(8, 32); break;
-            case 12: LAUNCH_BLOCK_SEL(12, 32); break;
-            case 16: LAUNCH_BLOCK_SEL(16, 32); break;
-            case 20: LAUNCH_BLOCK_SEL(20, 32); break;
-            default: launched = false; break;
-        }
-    } else {
-        switch (best.dot) {
-            case 8: LAUNCH_BLOCK_SEL(8, 16); break;
-            case 10: LAUNCH_BLOCK_SEL(10, 16); break;
-            case 14: LAUNCH_BLOCK_SEL(14, 16); break;
-            case 16: LAUNCH_BLOCK_SEL(16, 16); break;
-            case 20: LAUNCH_BLOCK_SEL(20, 16); break;
-            case 28: LAUNCH_BLOCK(28, 28, 16); break;
-            case 32: LAUNCH_BLOCK(32, 32, 16); break;
-            default: launched = false; break;
-        }
-    }
-#undef LAUNCH_BLOCK_SEL
-#undef LAUNCH_BLOCK
-    if (!launched) return BASD_EUNSUPPORTED;
-    if (sweeps_out) block_sweeps_kernel<<<(batch + 255) / 256, 256, 0, stream>>>(flags, batch, max_sweeps, sweeps_out);
-    colnorm_kernel<<<dim3((n + 3) / 4, batch), 256, 0, stream>>>(W, batch_stride, rows_dot, rows_tot, n, n_arr, colnorm,
-                                                                 colnorm_stride);
     BASD_RETURN_LAST();
 }
 
 // Two-pass solver (see jacobi_top_logged_kernel) for stacked square cores [M; L_b] (2n x n, leading dimension 2n).
-// Lane-element counts instantiated: n <= 4 EPL.
-static int twopass_epl(int n) {
-    static const int epls[] = {28, 36, 44, 50};
-    const size_t n_even = (n + 1) & ~1;
-    for (int e : epls)
-        if (n <= 4 * e) {
-            const size_t ld = 4 * e + (((4 * e / 8) % 2 == 0) ? 8 : 0);          // TwoPassShape<e>::LD
-            return sizeof(float) * (n_even * ld + 2 * n_even) <= BASD_JACOBI_LDS_LIMIT ? e : 0;   // n <= 196
-        }
-    return 0;
-}
-static bool stacked_lds_fits(int n) {              // the one-kernel LDS solver of basd_jacobi_onesided for a 2n x n core
-    const int n_even = (n + 1) & ~1, epl = 2 * ((n + 15) / 16);
-    static const int lds_epl[] = {4, 8, 12, 16, 20};
-    for (int e : lds_epl)
-        if (e >= epl) return (size_t)n_even * (16 * e + 4) * sizeof(float) <= BASD_JACOBI_LDS_LIMIT;
-    return false;
-}
 // Bytes of device workspace basd_jacobi_stacked_twopass needs (rotation log + defects + sweep counts); 0 when the
 // shape is not one it covers (cores that fit the one-kernel LDS solver: n <= 128, or n > 196).
 long basd_jacobi_twopass_workspace_bytes(int n, int batch, int max_sweeps) {
@@ -1204,41 +1189,23 @@ int basd_jacobi_stacked_twopass(float* W, long batch_stride, int n, int batch, f
                                 int max_sweeps, float tol_cos, void* workspace, int* sweeps_out, hipStream_t stream) {
     BASD_CHECK_ARG(W && colnorm && workspace && n > 1 && batch > 0 && max_sweeps > 0);
     BASD_CHECK_ARG(((uintptr_t)workspace & 7) == 0);
-    const int epl = twopass_epl(n);
-    if (!epl || stacked_lds_fits(n)) return BASD_EUNSUPPORTED;
+    const JacobiPlan p = twopass_plan(n);
+    if (!p.route || stacked_lds_fits(n)) return BASD_EUNSUPPORTED;
     const float tol = tol_cos > 0.f ? tol_cos : 1.2e-7f * sqrtf((float)n);
     const long n_even = (n + 1) & ~1;
     const long entries = (long)max_sweeps * (n_even - 1) * (n_even / 2);
     f32x2* rotlog = (f32x2*)workspace;
     float* dev = (float*)(rotlog + (long)batch * entries);
     int* sweeps = (int*)(dev + (long)batch * n);
-    int threads = (int)(((n_even / 2) * 4 + 63) / 64) * 64;
-    BASD_CHECK_ARG(threads <= 512);
-#define LAUNCH_2P(E)                                                                                                  \
-    do {                                                                                                              \
-        const size_t lds = sizeof(float) * ((size_t)n_even * TwoPassShape<E>::LD + 2 * (size_t)n_even);               \
-        if (lds > BASD_JACOBI_LDS_LIMIT) return BASD_EUNSUPPORTED;                                                    \
-        (void)hipFuncSetAttribute((const void*)jacobi_top_logged_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  BASD_JACOBI_LDS_LIMIT);                                                             \
-        jacobi_top_logged_kernel<E><<<batch, threads, lds, stream>>>(W, batch_stride, 2 * n, n, max_sweeps, tol, colnorm, \
-                                                                     colnorm_stride, rotlog, entries, dev, sweeps);   \
-        if (n <= 160) {                                                                                               \
-            const size_t lds2 = sizeof(float) * (size_t)n_even * TwoPassShape<10>::LD;                                \
-            jacobi_apply_log_kernel<10><<<dim3(batch, (n + 39) / 40), threads, lds2, stream>>>(                       \
-                W, batch_stride, 2 * n, n, n, rotlog, entries, dev, sweeps);                                          \
-        } else {                                                                                                      \
-            const size_t lds2 = sizeof(float) * (size_t)n_even * TwoPassShape<14>::LD;                                \
-            jacobi_apply_log_kernel<14><<<dim3(batch, (n + 55) / 56), threads, lds2, stream>>>(                       \
-                W, batch_stride, 2 * n, n, n, rotlog, entries, dev, sweeps);                                          \
-        }                                                                                                             \
-    } while (0)
-    switch (epl) {
-        case 28: LAUNCH_2P(28); break;
-        case 36: LAUNCH_2P(36); break;
-        case 44: LAUNCH_2P(44); break;
-        default: LAUNCH_2P(50); break;
-    }
-#undef LAUNCH_2P
+    BASD_CHECK_ARG(p.threads <= 512);
+    with_entry(TwoPassEpl{}, p.epl, [&](auto e) {
+        constexpr int E = e;
+        allow_lds((const void*)jacobi_top_logged_kernel<E>, p.lds, true);
+        jacobi_top_logged_kernel<E><<<batch, p.threads, p.lds, stream>>>(W, batch_stride, 2 * n, n, max_sweeps, tol, colnorm,
+                                                                         colnorm_stride, rotlog, entries, dev, sweeps);
+    });
+    if (n <= 160) launch_apply_log<10>(p, W, batch_stride, n, batch, rotlog, entries, dev, sweeps, stream);
+    else launch_apply_log<14>(p, W, batch_stride, n, batch, rotlog, entries, dev, sweeps, stream);
     if (sweeps_out) {
         hipError_t e = hipMemcpyAsync(sweeps_out, sweeps, sizeof(int) * (size_t)batch, hipMemcpyDeviceToDevice, stream);
         if (e != hipSuccess) return (int)e;
