@@ -32,6 +32,14 @@ import torch
 F32_EPS = float(torch.finfo(torch.float32).eps)
 
 
+def _compute(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """``x`` as the selector / loss functions take it in at compute dtype ``dtype``.  float32 (the default everywhere)
+    is the reference: tensors stay in the dtype the caller handed over and only the reference's own ``.float()`` casts
+    apply.  float64 is the high-precision evaluation of the same formulas that the GPU tests compare against: every
+    input is widened on entry, so no step rounds to fp32."""
+    return x if dtype == torch.float32 else x.to(dtype)
+
+
 # --------------------------------------------------------------------------- #
 # a10: extraction-layer placement                    (src/losses/combined.py:34-40)
 # --------------------------------------------------------------------------- #
@@ -52,31 +60,33 @@ def mp_threshold_factor(M: int, D: int) -> float:
     return (1 + q ** 0.5) ** 2
 
 
-def mp_rank_from_eigenvalues(eigvals: torch.Tensor, M: int, D: int) -> int:
+def mp_rank_from_eigenvalues(eigvals: torch.Tensor, M: int, D: int, dtype: torch.dtype = torch.float32) -> int:
     """eigvals: fp32 eigenvalues (any order).  Lower median, strict '>' against
-    the fp32-rounded threshold  (layer_selector.py:17-19)."""
-    ev, _ = torch.sort(eigvals.float())
+    the fp32-rounded threshold  (layer_selector.py:17-19).  ``dtype=torch.float64``: eigenvalues and threshold
+    stay in fp64."""
+    ev, _ = torch.sort(eigvals.to(dtype))
     n = ev.numel()
     sigma2 = float(ev[(n - 1) // 2])                # torch.median == lower median
     lam = sigma2 * mp_threshold_factor(M, D)        # float64 on the host
-    lam32 = torch.tensor(lam, dtype=torch.float32)  # tensor-vs-scalar compare is done in fp32
-    return int((ev > lam32).sum())
+    lam_t = torch.tensor(lam, dtype=dtype)          # tensor-vs-scalar compare is done in the tensor's dtype (fp32)
+    return int((ev > lam_t).sum())
 
 
 @torch.no_grad()
-def mp_rank(features: torch.Tensor) -> int:
+def mp_rank(features: torch.Tensor, dtype: torch.dtype = torch.float32) -> int:
     M, D = features.shape
-    x = features
+    x = _compute(features, dtype)
     # Gram on the smaller side, NOT centred          (layer_selector.py:12-15)
     gram = (x.T @ x) / M if M >= D else (x @ x.T) / M
-    return mp_rank_from_eigenvalues(torch.linalg.eigvalsh(gram), M, D)
+    return mp_rank_from_eigenvalues(torch.linalg.eigvalsh(gram), M, D, dtype)
 
 
 # --------------------------------------------------------------------------- #
 # a2: top-k PCA subspace                        (src/losses/layer_selector.py:23-37)
 # --------------------------------------------------------------------------- #
-def pca_subspace(z_flat: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
-    z = z_flat.float()
+def pca_subspace(z_flat: torch.Tensor, k: int,
+                 dtype: torch.dtype = torch.float32) -> tuple[torch.Tensor, torch.Tensor]:
+    z = z_flat.to(dtype)
     z = z - z.mean(dim=0, keepdim=True)
     _, S, Vh = torch.linalg.svd(z, full_matrices=False)
     return Vh[:k].T, S[:k]
@@ -121,11 +131,11 @@ def token_weights(attn: torch.Tensor, has_cls: bool, n_s: int) -> torch.Tensor:
 
 
 def procrustes_terms(
-    s: torch.Tensor, t: torch.Tensor, w: torch.Tensor
+    s: torch.Tensor, t: torch.Tensor, w: torch.Tensor, dtype: torch.dtype = torch.float32
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Per-sample (tr_s, tr_t, nuclear norm) of relational.py:36-48."""
-    s = s.float()
-    t = t.float()
+    s = s.to(dtype)
+    t = t.to(dtype)
     w3 = w.unsqueeze(-1)
     s_c = s - (w3 * s).sum(dim=1, keepdim=True)
     t_c = t - (w3 * t).sum(dim=1, keepdim=True)
@@ -145,9 +155,10 @@ def geometric_relational_loss(
     teacher_attn: torch.Tensor,
     *,
     has_cls_token: bool,
+    dtype: torch.dtype = torch.float32,
 ) -> torch.Tensor:
-    w = token_weights(teacher_attn, has_cls_token, student_tokens.shape[1])
-    tr_s, tr_t, nuc = procrustes_terms(student_tokens, teacher_tokens, w)
+    w = token_weights(_compute(teacher_attn, dtype), has_cls_token, student_tokens.shape[1])
+    tr_s, tr_t, nuc = procrustes_terms(student_tokens, teacher_tokens, w, dtype)
     return (tr_s + tr_t - 2.0 * nuc).mean()
 
 
@@ -188,30 +199,36 @@ def selector_forward(
     teacher_tokens: dict[int, torch.Tensor],
     teacher_attns: dict[int, torch.Tensor],
     extraction_indices: list[int],
+    dtype: torch.dtype = torch.float32,
 ) -> tuple[dict[int, torch.Tensor], dict[int, torch.Tensor], SelectorTrace]:
+    """``dtype=torch.float64``: the same formulas with every tensor widened on entry (``_compute``); ``state.ranks`` and
+    the trace then hold the fp64 evaluation."""
     t_keys = sorted(teacher_tokens.keys())                      # layer_selector.py:123
     D_s = state.proj_s.shape[0]
     D_t = teacher_tokens[t_keys[0]].shape[2]
+    teacher_tokens = {k: _compute(v, dtype) for k, v in teacher_tokens.items()}
+    teacher_attns = {k: _compute(v, dtype) for k, v in teacher_attns.items()}
+    proj_s, proj_t = _compute(state.proj_s, dtype), _compute(state.proj_t, dtype)
 
     # ranks + teacher subspaces, no grad                        (:69-74, :131-138)
     bases: dict[int, torch.Tensor] = {}
     sweights: dict[int, torch.Tensor] = {}
     with torch.no_grad():
         for key in t_keys:
-            z_t = teacher_tokens[key].reshape(-1, D_t) @ state.proj_t.T
-            state.ranks[key] = min(mp_rank(z_t), D_s - 1)
-            bases[key], sweights[key] = pca_subspace(z_t, state.ranks[key])
+            z_t = teacher_tokens[key].reshape(-1, D_t) @ proj_t.T
+            state.ranks[key] = min(mp_rank(z_t, dtype), D_s - 1)
+            bases[key], sweights[key] = pca_subspace(z_t, state.ranks[key], dtype)
 
     tok_stack = torch.stack([teacher_tokens[k] for k in t_keys])     # (:128)
     att_stack = torch.stack([teacher_attns[k] for k in t_keys])      # (:129)
-    tau_all = torch.nn.functional.softplus(state.log_temperatures)   # (:65-67)
+    tau_all = torch.nn.functional.softplus(_compute(state.log_temperatures, dtype))   # (:65-67)
 
     mixed_tok: dict[int, torch.Tensor] = {}
     mixed_att: dict[int, torch.Tensor] = {}
     trace = SelectorTrace(dict(state.ranks), {}, {})
     for i, s_layer in enumerate(extraction_indices):                 # (:143-150)
-        x = student_tokens[s_layer]
-        z_s = (x.reshape(-1, x.shape[2]) @ state.proj_s.T).float()   # (:86-88)
+        x = _compute(student_tokens[s_layer], dtype)
+        z_s = (x.reshape(-1, x.shape[2]) @ proj_s.T).to(dtype)       # (:86-88)
         z_s = z_s - z_s.mean(dim=0, keepdim=True)                    # (:90-91)
         Vh_s = torch.linalg.svd(z_s, full_matrices=False)[2]         # (:92)
         dists = []
@@ -236,7 +253,8 @@ def selector_forward(
 # --------------------------------------------------------------------------- #
 def uwso_combine(losses: list[torch.Tensor]) -> torch.Tensor:
     """combined.py:78-85.  w_i = (1/L_i)/sum_j(1/L_j) with detached L."""
-    eps = torch.finfo(losses[0].dtype).eps
+    # the clamp is a constant of the formula (the reference's losses are fp32), not a property of the compute dtype
+    eps = F32_EPS if losses[0].dtype == torch.float64 else torch.finfo(losses[0].dtype).eps
     inv = torch.stack([1.0 / v.detach().clamp(min=eps) for v in losses])
     w = inv / inv.sum()
     total = w[0] * losses[0]
@@ -263,15 +281,16 @@ def basd_forward(
     student_tokens: dict[int, torch.Tensor],
     teacher_tokens: dict[int, torch.Tensor],
     teacher_attns: dict[int, torch.Tensor],
+    dtype: torch.dtype = torch.float32,
 ) -> tuple[torch.Tensor, BASDTrace]:
-    ce = base_criterion(logits, targets)                                        # (:56)
+    ce = base_criterion(_compute(logits, dtype), targets)                       # (:56)
     mixed_tok, mixed_att, sel = selector_forward(
-        state, student_tokens, teacher_tokens, teacher_attns, layers)            # (:58-61)
+        state, student_tokens, teacher_tokens, teacher_attns, layers, dtype)     # (:58-61)
     geo = []
     for layer in layers:                                                        # (:63-75)
         aligned = resample_tokens(mixed_tok[layer], num_student_tokens)
         geo.append(geometric_relational_loss(
-            student_tokens[layer], aligned, mixed_att[layer], has_cls_token=teacher_has_cls))
+            student_tokens[layer], aligned, mixed_att[layer], has_cls_token=teacher_has_cls, dtype=dtype))
     geo_mean = torch.stack(geo).mean()                                          # (:76)
     total = uwso_combine([ce, geo_mean])                                        # (:78-85)
     return total, BASDTrace(ce.detach(), [g.detach() for g in geo], sel)

@@ -30,8 +30,10 @@ def _module(shape, ls):
                     teacher_has_cls_token=shape.has_cls).to(DEV)
 
 
-def test_mp_rank_golden(golden):
+@pytest.mark.parametrize("solver", ["tridiag", "jacobi"])
+def test_mp_rank_golden(golden, solver, monkeypatch):
     from basd_amd.losses import marchenko_pastur_rank
+    monkeypatch.setattr(ops, "EIG_SOLVER", solver)
     g = golden("mp_rank.npz")
     cases = [("m32_d192", 32, 192, 6), ("m128_d192", 128, 192, 10), ("m1000_d384", 1000, 384, 24),
              ("m12544_d384", 12544, 384, 48)]
@@ -642,10 +644,12 @@ def test_selector_forward_api_materialises_mixed_tensors(golden):
             np.testing.assert_allclose(a[:, :, 0, 1:].cpu().numpy(), g[f"attn_{l}_cls_row"], rtol=2e-3, atol=1e-6)
 
 
+@pytest.mark.parametrize("solver", ["tridiag", "jacobi"])
 @pytest.mark.parametrize("tag", ["vit", "cnn", "vit_same"])
-def test_estimate_ranks_golden(golden, tag):
+def test_estimate_ranks_golden(golden, tag, solver, monkeypatch):
     """GrassmannianLayerSelector._estimate_ranks (layer_selector.py:69-74) by itself: ``subspace_ranks`` against the
     ranks the imported reference produced on the same teacher tensors (exact)."""
+    monkeypatch.setattr(ops, "EIG_SOLVER", solver)
     g = golden("full_small.npz")
     shape, seed = S.SMALL[tag]
     mod = _module(shape, 0.01)
