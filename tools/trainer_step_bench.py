@@ -10,7 +10,12 @@ batch on the device, basd_amd.trivial_augment, one launch per batch ahead of the
 [--resize-crop]  (with --uint8: the batch is a pinned RaggedBatch of 500 x 375 decoded images, uploaded inside the step;
 basd_amd.resize makes both views, one launch)  [--jpeg-decode [serial|parallel]]  (with --resize-crop: the batch is a
 pinned JpegBatch of the same pictures as JPEG files (tools/jpeg_bench.make_streams), decoded by basd_amd.jpeg ahead of
-the resize launch; parallel: Trainer(jpeg_decode="parallel"), the entropy stage that decodes inside a segment)"""
+the resize launch; parallel: Trainer(jpeg_decode="parallel"), the entropy stage that decodes inside a segment)
+[--prefetch V [V ...]] [--windows 1]  (the step is fed from a list of --steps references to the batch through the
+trainer's DevicePrefetcher; V is a depth, or DEPTH:lowest for a side stream of the lowest priority; 0, the default, is
+the serial path.  Several values: --windows windows of --steps steps for each, alternating in this one process, every
+window a host clock around a device synchronise; then the loss alone, timed with events while the side stream holds
+the input work of a batch and while it is idle.  Prints GPU_MAX_HW_QUEUES as found in the environment.)"""
 import argparse, os, sys, time
 from types import SimpleNamespace
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,7 +37,19 @@ ap.add_argument("--uint8", action="store_true")
 ap.add_argument("--trivial-augment", action="store_true")
 ap.add_argument("--resize-crop", action="store_true")
 ap.add_argument("--jpeg-decode", nargs="?", const="serial", choices=("serial", "parallel"), default=None)
+ap.add_argument("--prefetch", nargs="+", default=["0"])
+ap.add_argument("--windows", type=int, default=1)
 args = ap.parse_args()
+
+
+def variant(text):
+    depth, _, priority = text.partition(":")
+    if not depth.isdigit() or priority not in ("", "default", "lowest"):
+        ap.error(f"--prefetch takes DEPTH or DEPTH:lowest (got {text!r})")
+    return text, int(depth), priority or "default"
+
+
+variants = [variant(v) for v in args.prefetch]
 if args.uint8 and args.mixup != "fused":
     ap.error("--uint8 needs --mixup fused")
 if args.trivial_augment and not args.uint8:
@@ -94,9 +111,35 @@ def timed(fn, n):
     return (time.perf_counter() - t0) / n * 1e3
 
 
-for _ in range(2):
-    out = tr.train_step(step_batch)
-step_ms = timed(lambda: tr.train_step(step_batch), args.steps)
+from basd_amd.prefetch import DevicePrefetcher
+feed = [step_batch] * args.steps
+prefetchers = {name: DevicePrefetcher(tr.prepare_batch, device=dev, depth=depth, priority=priority)
+               for name, depth, priority in variants}
+
+
+def window(name):
+    """--steps steps through the trainer's prefetcher, as _train_epoch feeds them (its metrics code aside)."""
+    global out
+    tr._prefetcher = prefetchers[name]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for prepared in tr._prefetcher.iterate(feed):
+        out = tr.step_prepared(prepared)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / args.steps * 1e3
+
+
+for name in prefetchers:                                   # warm-up: every variant once (its stream, its events)
+    tr._prefetcher = prefetchers[name]
+    for prepared in tr._prefetcher.iterate(feed[:2]):
+        out = tr.step_prepared(prepared)
+windows = {name: [] for name in prefetchers}
+losses = {name: [] for name in prefetchers}                # the last step's loss of every window
+for _ in range(args.windows):
+    for name in prefetchers:
+        windows[name].append(round(window(name), 2))
+        losses[name].append(round(float(out["loss"]), 4))
+step_ms = sum(windows[variants[0][0]]) / args.windows
 acx = torch.autocast("cuda", dtype=ac, enabled=ac is not None)
 
 
@@ -127,8 +170,33 @@ def loss_only():
 
 loss_only()
 l_ms = timed(loss_only, args.steps)
+
+
+def loss_by_events(side):
+    """The loss alone between two events on its own stream; with ``side`` the input work of one batch is queued on
+    that stream ahead of every call, so the loss's four streams share the hardware queues with a fifth busy one."""
+    pairs = []
+    torch.cuda.synchronize()
+    for _ in range(args.steps):
+        if side is not None:
+            with torch.cuda.stream(side):
+                tr.prepare_batch(step_batch)
+        pairs.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+        pairs[-1][0].record()
+        loss_only()
+        pairs[-1][1].record()
+    torch.cuda.synchronize()
+    return round(sum(a.elapsed_time(b) for a, b in pairs) / args.steps, 2)
+
+
+loss_events = {"side_idle": loss_by_events(None)}
+for name, pf in prefetchers.items():
+    if pf.stream is not None:
+        loss_events[f"side_busy[{name}]"] = loss_by_events(pf.stream)
 print({"batch": B, "dtype": args.dtype, "optimizer": args.optimizer, "mixup": args.mixup, "teacher": args.teacher,
        "attn_capture": args.attn_capture, "uint8": args.uint8, "trivial_augment": args.trivial_augment, "resize_crop": args.resize_crop,
-       "jpeg_decode": args.jpeg_decode, "step_ms": round(step_ms, 2), "images_per_s": round(B / step_ms * 1e3, 1),
+       "jpeg_decode": args.jpeg_decode, "prefetch": args.prefetch, "steps": args.steps, "step_ms": round(step_ms, 2),
+       "step_ms_windows": windows, "loss_windows": losses, "images_per_s": round(B / step_ms * 1e3, 1),
        "student_fwd_nograd_ms": round(s_ms, 2), "teacher_fwd_ms": round(t_ms, 2), "loss_fwd_bwd_ms": round(l_ms, 2),
+       "loss_fwd_bwd_ms_by_events": loss_events, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "unset"),
        "loss_share": round(l_ms / step_ms, 3), "loss": float(out["loss"]), "ranks": dict(tr.basd_loss.layer_selector.subspace_ranks)})

@@ -24,6 +24,15 @@ def require_gpu(device_or_tensor, what=None) -> None:
                            + ("" if what is None else f"; {what} live on {device}"))
 
 
+def retire(state) -> None:
+    """Called on persistent device state (``None``: nothing yet) right before it is replaced by a larger one: the last
+    launches that read it may be on another stream than the one it was allocated on (a ``DevicePrefetcher``'s), so the
+    allocator is told to hand the memory out again only behind the current stream's work.  Nothing is done for a
+    tensor allocated on the current stream."""
+    if state is not None and state.is_cuda:
+        state.record_stream(torch.cuda.current_stream(state.device))
+
+
 def lives_on(owner: torch.device, device: torch.device) -> bool:
     """An owner without an index (``cuda``) takes every device of its type."""
     return device.type == owner.type and owner.index in (None, device.index)
@@ -105,7 +114,8 @@ class RecordTable:
     def stage(self, count: int, device: torch.device) -> np.ndarray:
         nbytes = max(count, 1) * self.record_dtype.itemsize
         if self.table is None or self.table.numel() < nbytes:
-            self.table = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            retire(self.table)
+            self.table =torch.empty(nbytes, dtype=torch.uint8, device=device)
             self._host = [(torch.empty(nbytes, dtype=torch.uint8).pin_memory(), torch.cuda.Event())
                           for _ in range(self.ring)]
         if self._status is None:

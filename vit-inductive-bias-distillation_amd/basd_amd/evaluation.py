@@ -111,7 +111,7 @@ def _label_smoothing_of(criterion) -> float:
 @torch.no_grad()
 def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_classes: int, valid_indices=None,
                    distributed: bool = False, image_stats=None, input_dtype=None, resize_crop=None,
-                   jpeg_decode=None) -> dict:
+                   jpeg_decode=None, prefetch: int = 0, prefetch_stream=None) -> dict:
     """The reference's ``evaluate_model``: batches are dicts with ``pixel_values`` and ``label``; returns ``val_acc``,
     ``val_acc_top5`` (percent) and ``loss`` (mean of ``criterion`` over the samples); fewer than 5 evaluated classes
     raise ``ValueError``.  ``distributed=True``: every rank iterates its own shard and the counts are summed over the
@@ -125,8 +125,15 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
     images, ``collate_fn=collate_ragged``) instead of ``pixel_values``: one launch makes the clean view (``Resize ->
     CenterCrop``), which then takes the uint8 path above, so ``image_stats`` is needed (``ValueError`` otherwise).
     ``jpeg_decode``: a ``basd_amd.jpeg.JpegDecoder`` (it needs ``resize_crop``); with it ``images`` may be a ``JpegBatch``
-    of the files' bytes (``collate_fn=collate_jpeg``), decoded on the device ahead of the resize launch."""
+    of the files' bytes (``collate_fn=collate_jpeg``), decoded on the device ahead of the resize launch.
+    ``prefetch``: an int >= 0 (``ValueError`` otherwise); the input half of up to that many batches (transfer, decode,
+    resize, conversion, labels) runs ahead on a side stream (``basd_amd.prefetch.DevicePrefetcher``) while the model
+    and the metrics launch of the batch before stay on the caller's; 0, the default, is the serial loop.
+    ``prefetch_stream``: a ``DevicePrefetcher``'s ``.stream`` to use for it instead of a new one.  ``resize_crop`` and
+    ``jpeg_decode`` belong to this call until it returns."""
     label_smoothing = _label_smoothing_of(criterion)
+    if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
+        raise ValueError(f"prefetch must be an int >= 0 (got {prefetch!r})")
     if resize_crop is not None and image_stats is None:
         raise ValueError("resize_crop needs image_stats=(mean, std): its uint8 batches are converted and normalised on "
                          "the device; got image_stats=None")
@@ -142,7 +149,9 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
         from .augment import BatchMixer, MixParams
         mean, std = image_stats
         converter = BatchMixer(num_classes, mean=mean, std=std, out_dtype=input_dtype, device=device)
-    for batch in data_loader:
+
+    def prepare(batch):
+        """The input half of a batch: transfer, optional decode, resize of the clean view, conversion, labels."""
         if "images" in batch and "pixel_values" not in batch:
             if resize_crop is None:
                 raise TypeError("a batch of decoded 'images' needs resize_crop=ResizeCrop(...); got resize_crop=None")
@@ -161,6 +170,11 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
         targets = batch["label"].to(device, non_blocking=True)
         if inputs.dtype == torch.uint8:
             inputs, _ = converter(inputs, None, MixParams("none"))
+        return inputs, targets
+
+    from .prefetch import DevicePrefetcher
+    prefetcher = DevicePrefetcher(prepare, device=device, depth=prefetch, stream=prefetch_stream if prefetch else None)
+    for inputs, targets in prefetcher.iterate(data_loader):
         acc.update(model(inputs), targets)
     if distributed:
         acc.all_reduce()

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._launch import RecordTable, lives_on, raw_stream, require_gpu
+from ._launch import RecordTable, lives_on, raw_stream, require_gpu, retire
 from .resize import RaggedBatch
 
 __all__ = ["JpegHeader", "parse_jpeg", "UnsupportedJpeg", "JpegBatch", "pack_jpegs", "collate_jpeg", "JpegDecoder",
@@ -499,7 +499,8 @@ class JpegDecoder:
         if bool((_blocks_of(rec) * 192 > need).any()):
             raise ValueError("a record describes more blocks than the batch's workspace holds")
         if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=batch.device)
+            retire(self.workspace)
+            self.workspace =torch.empty(need, dtype=torch.uint8, device=batch.device)
         self.used_bytes = need
         self._records.stage(B, batch.device)[...] = rec
         args = (batch.data.data_ptr(), batch.data.numel(), out.data_ptr(), out.numel(), B, self._records.upload(),

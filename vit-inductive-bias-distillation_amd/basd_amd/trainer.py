@@ -114,13 +114,23 @@ class Trainer:
     all-reduce and with the ``grad_scale`` the update gets, so every rank forms the same coefficient and the same verdict.
     With either, ``train_step`` also returns ``"grad_norm"`` and ``_train_epoch`` ``"grad_norm"`` (the mean over the steps
     that were not skipped, accumulated on the device) and ``"skipped_steps"`` (this epoch's count, one read at its end).
-    A skipped step still advances the optimizer's ``k`` (see ``AdamWScheduleFree``)."""
+    A skipped step still advances the optimizer's ``k`` (see ``AdamWScheduleFree``).
+    ``prefetch``: an int >= 0.  ``_train_epoch`` and ``evaluate`` run ``prepare_batch`` (the validation loop: its input
+    half) for up to ``prefetch`` batches ahead of the one whose step runs, on one side stream
+    (``basd_amd.prefetch.DevicePrefetcher``); 0, the default, is the serial loop.  It costs the memory of ``prefetch``
+    prepared batches.  The draws stay inside ``prepare_batch``, in their order and the batches in theirs, so a seeded run
+    prepares bit-identical batches with and without it; the one exception is a model that itself draws from the CPU
+    generator in its forward (dropout in a CPU model): its draws fall between other batches' draws.  A model on the GPU
+    draws from the device generator and is unaffected.  While an epoch or a validation runs, the stage objects of this
+    trainer belong to its prefetcher: nothing else may call them."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
                  resize_crop: bool = False, jpeg_decode=False, max_grad_norm=None,
-                 skip_nonfinite: bool = False) -> None:
+                 skip_nonfinite: bool = False, prefetch: int = 0) -> None:
+        if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
+            raise ValueError(f"prefetch must be an int >= 0 (got {prefetch!r})")
         self._guarded = max_grad_norm is not None or bool(skip_nonfinite)
         self._skipped_seen = 0
         if self._guarded and optimizer != "schedulefree":
@@ -193,6 +203,9 @@ class Trainer:
                                  "resize launch takes); got resize_crop=False")
             from .jpeg import JpegDecoder
             self._decoder = JpegDecoder(self.device, entropy="parallel" if jpeg_decode == "parallel" else "serial")
+        from .prefetch import DevicePrefetcher
+        self.prefetch = prefetch
+        self._prefetcher = DevicePrefetcher(self.prepare_batch, device=self.device, depth=prefetch)
         self.best_val_acc = 0.0
         self.metrics_history = defaultdict(list)
         self._params = [p for p in student_model.parameters() if p.requires_grad]
@@ -240,7 +253,11 @@ class Trainer:
         views = self._resizer(images.to(dev, non_blocking=True), batch.get("crop_params"))
         return views["clean"], views["augmented"]
 
-    def train_step(self, batch: dict) -> dict:
+    def prepare_batch(self, batch: dict) -> dict:
+        """The input half of a step, everything ahead of the model forwards: the transfer, the views, the augmentation
+        and the mixing, with the checks that raise ``TypeError``.  Returns ``clean``, ``augmented``, ``targets`` and
+        ``mixed_targets`` on the device.  It draws crop, augment and mix, in that order, on the global CPU generator and
+        touches neither model, so it may run ahead of the step before it (``prefetch``)."""
         dev = self.device
         clean, student_imgs = self.prepare_views(batch)
         targets = batch["label"].to(dev, non_blocking=True)
@@ -260,6 +277,13 @@ class Trainer:
             student_imgs, mixed_targets = self._mixer(student_imgs, targets)
         elif self.mixup:
             student_imgs, mixed_targets = mixup_cutmix(student_imgs, targets, self.config.model.num_classes)
+        return {"clean": clean, "augmented": student_imgs, "targets": targets, "mixed_targets": mixed_targets}
+
+    def step_prepared(self, prepared: dict) -> dict:
+        """The rest of the step on what ``prepare_batch`` returned: both forwards, the loss, the backward, the update."""
+        dev = self.device
+        clean, student_imgs = prepared["clean"], prepared["augmented"]
+        targets, mixed_targets = prepared["targets"], prepared["mixed_targets"]
         ac = torch.autocast(dev.type, dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None)
         with ac:
             logits, s_tokens = capture._extract_student(self.model, student_imgs, self.basd_loss.token_layers,
@@ -281,6 +305,9 @@ class Trainer:
         if self._guarded:
             out["grad_norm"] = self.optimizer.last_grad_norm()
         return out
+
+    def train_step(self, batch: dict) -> dict:
+        return self.step_prepared(self.prepare_batch(batch))
 
     def _optimizer_mode(self, train: bool) -> bool:
         """``optimizer.train()`` / ``optimizer.eval()`` where the optimizer has them (reference trainer.py:180,184);
@@ -318,8 +345,8 @@ class Trainer:
             norm_steps = torch.zeros((), device=self.device)
         self.model.train()
         self._optimizer_mode(True)
-        for batch in train_loader:
-            out = self.train_step(batch)
+        for prepared in self._prefetcher.iterate(train_loader):
+            out = self.step_prepared(prepared)
             total_loss += out["loss"] * out["n"]
             correct += out["correct"]
             total += out["n"]
@@ -357,7 +384,8 @@ class Trainer:
         stats = None if self.image_stats is None else self.image_stats["augmented"]
         return evaluate_model(model, val_loader, self.criterion, num_classes=self.config.model.num_classes,
                               distributed=distributed, image_stats=stats, input_dtype=self.mix_dtype,
-                              resize_crop=self._resizer, jpeg_decode=self._decoder)
+                              resize_crop=self._resizer, jpeg_decode=self._decoder, prefetch=self.prefetch,
+                              prefetch_stream=self._prefetcher.stream)
 
     def train(self, train_loader, val_loader=None, start_epoch: int = 0, *, evaluate=None, on_epoch_end=None) -> dict:
         """The reference's epoch loop (trainer.py:171-216): ``_train_epoch``, validation, ``metrics_history``,
