@@ -398,7 +398,7 @@ int basd_token_weights(const void* const* attn_ptrs, int dtype, const float* mix
 
 /* Student half of relational.py:36-45 and the adjoint of combined.py:9-14:
  * mu = sum_n w_n x_n, tr_s = sum_n w_n |x_n - mu|^2 (as (B, ceil(D/64)) per-slab partials),
- * A' = I_interp^T diag(w) (X - 1 mu^T). */
+ * A' = I_interp^T diag(w) (X - 1 mu^T).  The general per-layer form: any row alignment, any number of tokens. */
 int basd_student_project(const void* x, int dtype, long sb, long sn, int B, int n_s, int n_t, int D,
                          const float* omega, const int* tap0, const int* tap1, const float* lam, const int* range0,
                          const int* range1, float* mu, float* tr_s, float* a_prime, hipStream_t stream);
@@ -485,7 +485,8 @@ int basd_student_grad_fused(const void* const* x_ptrs, int dtype, long sb, long 
  * front of the caller's stream).  All fields are 8 bytes wide; pointers are device memory except student_host_ptrs.
  *   G = 1: the teacher side is shared by all layers (one teacher layer: mixing weights exactly 1), else G = E.
  *   n = min(n_s, n_t): the core grid.  Arrays: omega (G,B,n_s), omega_t (G,B,n), raw (G,B,n_a) nullable,
- *   mu_t (G,B,d_t), tc (G,B,n,d_t), mu_s (E,B,d_s), tr_part (E,B,ceil(d_s/32)), tr_s/tr_t/nuc/loss_b (E,B),
+ *   mu_t (G,B,d_t), tc (G,B,n,d_t), mu_s (E,B,d_s), tr_part (plan field 12; at most E*B*ceil(d_s/32)),
+ *   tr_s/tr_t/nuc/loss_b (E,B),
  *   a_prime (E,B,n,d_s), g_all/l_all ((E+G)B,n,n) fp64, W (EB,n,2n), sigma (EB,n),
  *   jflags basd_jacobi_workspace_ints(EB, max_sweeps) ints, sweeps (EB) ints nullable, k_prime (EB,n,n) nullable,
  *   h (EB,n,d_s) + dx (E,B,n_s,d_s) + grad_layers (E): only for the gradients. */
@@ -513,18 +514,35 @@ typedef struct BasdProcrustesArgs {
      * uw_out (4 + 2 E floats) receives w_ce, w_geo, total, geo, then E x w_geo / E, then the E per-layer means.  The
      * student gradients (dx) are then those of `total` for a unit upstream gradient and grad_layers is ignored. */
     const float* uw_ce; float* uw_out;
-    /* nullable: basd_jacobi_twopass_workspace_bytes(n, E*B, max_sweeps) bytes; the SVD then takes
-     * basd_jacobi_stacked_twopass where that covers the shape */
+    /* nullable: basd_jacobi_twopass_workspace_bytes(n, E*B, max_sweeps) bytes; offered, the SVD of stacked cores
+     * takes basd_jacobi_stacked_twopass where that covers the shape (plan field 7) */
     void* jac_ws;
-    /* nullable, only read when `raw` is set (gradients through the mixing weights): E*B * 2n*n floats; the transposed
-     * route is then taken where basd_jacobi_plain4_fits(n) and U Sigma is rebuilt here (basd_ustack_from_transposed);
-     * sigma_u: E*B * n floats, the norms of its columns (what the backward pairs with w_stack) */
+    /* nullable, only read when `raw` is set (gradients through the mixing weights): E*B * 2n*n floats.  Offered, the
+     * planner may take the transposed cores for such a call and U Sigma is rebuilt here (basd_ustack_from_transposed);
+     * sigma_u: E*B * n floats, the norms of its columns (what the backward pairs with w_stack).  Plan field 11 says
+     * whether the backward finds U Sigma here or in W / sigma: when the stacked cores are taken, neither is written. */
     float* w_stack; float* sigma_u;
 } BasdProcrustesArgs;
 int basd_procrustes_forward_fused(const BasdProcrustesArgs* args, hipStream_t stream);
-/* Test / tuning hook: 0 = always the stacked cores [M; L_b] (riding rows); 1 = the transposed cores where they apply
- * (default: no gradient through the mixing weights, >= 128 cores, basd_jacobi_plain4_fits(n)); 2 = the same for any
- * batch; negative = keep.  Process-wide. */
+/* The routes basd_procrustes_forward_fused takes for `args` under the current hooks (host only: no HIP call, usable
+ * without a GPU; pointers are tested for presence and 16-byte alignment, never dereferenced, so any non-null aligned
+ * value stands for "offered").  One planner (csrc/procrustes_plan.h) answers here and in the call.  out20:
+ *    0 teacher centring: 1 stream, four features per thread; 2 stream; 3 all groups in one launch; 4 per group
+ *    1 student projection: 1 all layers in one launch, 2 per layer;  2 features per trace slab (32 / 64);  3 slabs
+ *    4 teacher Gram split (0 / 1);  5 Cholesky: 1 in LDS, 2 blocked;  6 cores: 1 transposed, 2 stacked [M; L_b]
+ *    7 SVD: 1 one-sided Jacobi on the transposed cores, 2 basd_jacobi_stacked_twopass with jac_ws (one-sided where
+ *      that does not cover the order), 3 one-sided on the stacked cores
+ *    8 finish: 1 basd_procrustes_finish_transposed, 2 basd_procrustes_finalize + basd_kprime_from_transposed,
+ *      3 basd_procrustes_finalize, 4 the same with K' by its tiled kernel
+ *    9 U Sigma rebuilt into w_stack (0 / 1);  10 student gradient: 0 none, 1 fused, 2 basd_gemm_tn + multi
+ *   11 U Sigma afterwards in: 1 W (with sigma), 2 w_stack (with sigma_u)
+ *   12 floats of tr_part the projection writes;  13 floats of W the stream centring borrows
+ *   14..19 dynamic LDS bytes of the centring, projection, Gram, Cholesky, finish and fused-gradient kernels (0: none)
+ * A stage with no route is 0 and the status BASD_EUNSUPPORTED; arguments the call rejects give BASD_EINVAL. */
+int basd_procrustes_plan_query(const BasdProcrustesArgs* args, long* out20);
+/* Test / tuning hook, read by the planner: 0 = always the stacked cores [M; L_b] (riding rows); 1 = the transposed
+ * cores where they apply (default: >= 128 cores, basd_jacobi_plain4_fits(n), and -- with a gradient through the mixing
+ * weights -- w_stack offered); 2 = the same for any batch; negative = keep.  Process-wide. */
 int basd_procrustes_tuning(int transposed_cores);
 
 /* The two pieces of the transposed route (relational.py:47-48 and its autograd): M = L_a^T L_b alone, row-major and

@@ -1,9 +1,9 @@
 // Records what the host side of csrc/jacobi.hip launches, without a GPU and without the HIP runtime.
 //
-// jacobi.o needs eleven runtime symbols; this file supplies stand-ins for the ten that are HIP's (atexit is libc's),
-// so the object links into a plain program.  The stand-ins launch nothing: they print the kernel name, grid, block
-// and dynamic LDS bytes of every launch, every function attribute that is set and the byte count of every fill /
-// copy.  Two builds of this program -- one against the jacobi.hip of a parent commit, one against the working tree --
+// jacobi.o needs eleven runtime symbols; hip_trace_standins.h supplies stand-ins for the ten that are HIP's (atexit is
+// libc's), so the object links into a plain program.  The stand-ins launch nothing: they print the kernel name, grid,
+// block and dynamic LDS bytes of every launch, every function attribute that is set and the byte count of every fill
+// / copy.  Two builds of this program -- one against the jacobi.hip of a parent commit, one against the working tree --
 // run over the same sweep of shapes must print the same bytes: that is the proof that a change to the dispatcher left
 // the launch sequences alone.  (Scalar kernel arguments are not seen: those are compared by eye in the diff.)
 //
@@ -12,99 +12,7 @@
 //   ./jacobi_dispatch_trace onesided | tall | twopass | queries > trace.txt      (a summary line goes to stderr)
 //
 // Runs of identical consecutive launches (the rounds of the block solver) are folded into one line with a count.
-#include <cstddef>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cxxabi.h>
-#include <map>
-#include <set>
-#include <string>
-
-// ---- the slice of the HIP ABI that a compiled .hip object uses --------------------------------------------------
-struct dim3 { uint32_t x, y, z; };
-typedef void* hipStream_t;
-
-static std::map<const void*, std::string> g_kernels;   // host stub -> demangled kernel name
-static std::string g_seq, g_last;                       // launch sequence of the current call; its last line
-static long g_repeat = 0;
-static struct { dim3 grid, block; size_t lds; hipStream_t stream; } g_config;
-
-static void flush_last() {
-    if (g_last.empty()) return;
-    g_seq += "  " + g_last;
-    if (g_repeat > 1) g_seq += " x" + std::to_string(g_repeat);
-    g_seq += "\n";
-    g_last.clear();
-    g_repeat = 0;
-}
-static void record(const std::string& line) {
-    if (line == g_last) { ++g_repeat; return; }
-    flush_last();
-    g_last = line;
-    g_repeat = 1;
-}
-static std::string kernel_name(const void* f) {
-    auto it = g_kernels.find(f);
-    return it == g_kernels.end() ? "<unregistered>" : it->second;
-}
-
-extern "C" {
-void** __hipRegisterFatBinary(const void*) { static void* handle; return &handle; }
-void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterFunction(void**, const void* host_fn, char*, const char* device_name, unsigned, void*, void*, void*,
-                           void*, int*) {
-    int status = 0;
-    char* d = abi::__cxa_demangle(device_name, nullptr, nullptr, &status);
-    std::string name = status == 0 && d ? d : device_name;
-    free(d);
-    const size_t paren = name.find('(');                // keep name and template arguments, drop the parameter list
-    if (paren != std::string::npos) name.resize(paren);
-    if (name.rfind("void ", 0) == 0) name.erase(0, 5);
-    g_kernels[host_fn] = name;
-}
-int __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
-    g_config = {grid, block, lds, stream};
-    return 0;
-}
-int __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* lds, hipStream_t* stream) {
-    *grid = g_config.grid; *block = g_config.block; *lds = g_config.lds; *stream = g_config.stream;
-    return 0;
-}
-int hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t lds, hipStream_t) {
-    char buf[160];
-    snprintf(buf, sizeof buf, " grid=%u,%u,%u block=%u,%u,%u lds=%zu", grid.x, grid.y, grid.z, block.x, block.y, block.z, lds);
-    record("launch " + kernel_name(f) + buf);
-    return 0;
-}
-int hipFuncSetAttribute(const void* f, int attr, int value) {
-    record("attr " + kernel_name(f) + " " + std::to_string(attr) + "=" + std::to_string(value));
-    return 0;
-}
-int hipGetLastError(void) { return 0; }
-int hipMemsetAsync(void*, int value, size_t bytes, hipStream_t) {
-    record("memset value=" + std::to_string(value) + " bytes=" + std::to_string(bytes));
-    return 0;
-}
-int hipMemcpyAsync(void*, const void*, size_t bytes, int kind, hipStream_t) {
-    record("memcpy kind=" + std::to_string(kind) + " bytes=" + std::to_string(bytes));
-    return 0;
-}
-
-// ---- the entry points under test (include/basd_hip.h) -----------------------------------------------------------
-int basd_jacobi_workspace_ints(int batch, int max_sweeps);
-int basd_jacobi_max_rows(void);
-int basd_jacobi_plain4_fits(int n);
-int basd_jacobi_lds_square_fits(int n);
-int basd_jacobi_tuning(int lanes_per_pair);
-int basd_jacobi_ordering(int odd_even);
-int basd_jacobi_onesided(float* W, long batch_stride, int rows_dot, int rows_tot, int n, int batch, const int* n_arr,
-                         float* colnorm, int colnorm_stride, int max_sweeps, float tol_cos, int* flags, int* sweeps_out,
-                         hipStream_t stream);
-long basd_jacobi_twopass_workspace_bytes(int n, int batch, int max_sweeps);
-int basd_jacobi_stacked_twopass(float* W, long batch_stride, int n, int batch, float* colnorm, int colnorm_stride,
-                                int max_sweeps, float tol_cos, void* workspace, int* sweeps_out, hipStream_t stream);
-}
+#include "hip_trace_standins.h"
 
 // never dereferenced: the stand-ins launch nothing
 static float* const kW = (float*)0x10000;
@@ -114,17 +22,6 @@ static int* const kSweeps = (int*)0x40000;
 static int* const kOrders = (int*)0x50000;
 static void* const kWorkspace = (void*)0x60000;
 static const int kMaxSweeps = 2;
-
-static long g_calls = 0;
-static std::set<std::string> g_distinct;
-
-static void finish_call(const char* what, int rc) {
-    flush_last();
-    printf("%s rc=%d\n%s", what, rc, g_seq.c_str());
-    ++g_calls;
-    g_distinct.insert(g_seq);
-    g_seq.clear();
-}
 
 static void onesided(int rows_dot, int rows_tot, int n, int batch, bool orders, bool with_flags, int lanes, int ordering) {
     char what[160];

@@ -19,8 +19,9 @@ import os
 _FLOATS = (torch.float32, torch.bfloat16)       # consumed in place; DTYPE_CODES has the kernels' codes
 MAX_SWEEPS = 20
 TWO_PASS_SVD = True      # test hook: False sends cores of 129..196 tokens through the block solver instead
-TRANSPOSED_MIX_GRAD = True   # test hook: False keeps the stacked cores (riding rows) whenever the mixing weights need a gradient;
-                             # "force": the transposed route also for small batches (with basd_procrustes_tuning(2))
+TRANSPOSED_MIX_GRAD = True   # test hook: is the buffer for U Sigma rebuilt from the transposed cores offered when the mixing weights
+                             # need a gradient?  False: no (stacked cores, riding rows); True / "force": yes -- where the
+                             # transposed cores are then taken is the C planner's decision (basd_procrustes_tuning)
 TWO_PASS_LOG_LIMIT = 16 << 30     # bytes of rotation log above which the block solver is used (cfg-4: 1.6 GB per call)
 # Symmetric eigen-solver for the selector's D_s x D_s Grams when only eigenvalues / leading eigenvectors are
 # needed: "tridiag" (Householder + bisection + inverse iteration) or "jacobi" (block one-sided Jacobi).
@@ -612,8 +613,23 @@ class _ProcrustesPlan:
     launches on ONE stream, so it is allocated once and reused by every step; what outlives the call -- the tensors kept
     for the backward and the student gradients handed to autograd -- is allocated per call (two ``torch.empty``)."""
 
+    # names of the routes basd_procrustes_plan_query answers with (include/basd_hip.h), in its order
+    ROUTE_FIELDS = ("center", "project", "slab_width", "slabs", "gram_split", "chol", "cores", "svd", "finish",
+                    "rebuild_usigma", "grad", "usigma_in", "tr_part_floats", "w_borrow_floats", "lds_center",
+                    "lds_project", "lds_gram", "lds_chol", "lds_finish", "lds_grad")
+    TRANSPOSED, TWO_PASS, IN_W_STACK = 1, 2, 2      # values of cores, svd, usigma_in
+
+    def query_routes(self) -> dict:
+        """The C planner's routes for ``self.args`` under the hooks as they stand (no HIP call)."""
+        import ctypes
+        out = (ctypes.c_long * len(self.ROUTE_FIELDS))()
+        status = _lib.query("basd_procrustes_plan_query", ctypes.addressof(self.args), ctypes.cast(out, ctypes.c_void_p))
+        if status != 0:
+            raise RuntimeError(f"basd_procrustes_plan_query failed with status {status} (invalid argument / unsupported shape)")
+        return dict(zip(self.ROUTE_FIELDS, out))
+
     def __init__(self, E, L, B, n_s, d_s, n_t, d_t, H, A, has_cls, need_bwd, need_mix_grad, want_sweeps, want_dx,
-                 want_uw, dev):
+                 want_uw, s_layout, t_layout, dev):
         import ctypes
         self.E, self.L, self.B, self.n_s, self.d_s, self.n_t, self.d_t = E, L, B, n_s, d_s, n_t, d_t
         n_a = A - (1 if has_cls else 0)
@@ -624,7 +640,6 @@ class _ProcrustesPlan:
         self.atp = taps(n_a, n_s, dev)
         G = self.G = 1 if L == 1 else E          # softmax over one layer is exactly 1: the teacher side is shared
         f32 = dict(device=dev, dtype=torch.float32)
-        slabs = (d_s + 31) // 32
         EB, GB = E * B, G * B
         self.need_bwd, self.need_mix_grad, self.want_dx, self.want_uw = need_bwd, need_mix_grad, want_dx, want_uw
         # ---- kept sizes (fresh per call): omega, mu_s, a_prime, k_prime, terms (4, E, B), uw
@@ -642,35 +657,53 @@ class _ProcrustesPlan:
         self.l_all = torch.empty((EB + GB, n, n), device=dev, dtype=torch.float64)
         self.W = torch.empty((EB, n, 2 * n), **f32)        # memory == column-major (2n x n)
         self.tc = torch.empty((G, B, n, d_t), **f32)
-        sizes = [GB * n, GB * d_t, EB * slabs, EB * n]
-        padded = [(c + 63) // 64 * 64 for c in sizes]
-        self.omega_t, self.mu_t, self.tr_part, self.sigma = (
-            piece[:c] for piece, c in zip(torch.split(torch.empty((sum(padded),), **f32), padded), sizes))
         self.ints = torch.empty((_lib.query("basd_jacobi_workspace_ints", EB, MAX_SWEEPS) + EB,), device=dev,
                                 dtype=torch.int32)
         self.sweeps = self.ints[-EB:] if want_sweeps else None
-        transposed_mix = bool(need_mix_grad and need_bwd and _lib.query("basd_jacobi_plain4_fits", n)
-                              and (EB >= 128 or TRANSPOSED_MIX_GRAD == "force") and TRANSPOSED_MIX_GRAD)
-        jac_bytes = _lib.query("basd_jacobi_twopass_workspace_bytes", n, EB, MAX_SWEEPS) \
-            if TWO_PASS_SVD and not transposed_mix else 0
-        if jac_bytes > TWO_PASS_LOG_LIMIT or (jac_bytes > (256 << 20)
-                                              and jac_bytes > torch.cuda.mem_get_info(dev)[0] // 2):
-            jac_bytes = 0       # very large batches / little free memory: the block solver needs no log
-        self.jac_ws = torch.empty((jac_bytes // 8 + 1,), device=dev, dtype=torch.int64) if jac_bytes > 0 else None
         self.h = torch.empty((E, B, n, d_s), **f32) if want_dx else None
-        # gradients through the mixing weights read U Sigma (the top half of the stacked cores): where the forward takes
-        # the transposed route (cores the plain LDS solver holds), it is rebuilt into this buffer
-        self.w_stack = None
-        self.sigma_u = None
-        if transposed_mix:
-            self.w_stack = torch.empty((EB, n, 2 * n), **f32)
-            self.sigma_u = torch.empty((EB, n), **f32)
         self.host_ptrs = (ctypes.c_void_p * E)()
 
         a = self.args = _lib.ProcrustesArgs()
         a.student_host_ptrs = ctypes.cast(self.host_ptrs, ctypes.c_void_p)
         (a.E, a.L, a.G, a.B, a.n_s, a.n_t, a.d_s, a.d_t, a.H, a.A, a.has_cls, a.n_a, a.n, a.max_sweeps) = \
             E, L, G, B, n_s, n_t, d_s, d_t, H, A, int(has_cls), n_a, n, MAX_SWEEPS
+        a.s_dtype, a.s_sb, a.s_sn, a.s_aligned = s_layout
+        a.t_dtype, a.t_sb, a.t_sn, a.t_sd = t_layout
+        a.g_splits = g_splits
+        a.g_slabs = self.g_all[EB + GB:].data_ptr() if g_splits > 1 else None
+        a.tc, a.W = self.tc.data_ptr(), self.W.data_ptr()
+        # Which routes the call will take is the C planner's decision.  It is asked with what this call offers: the
+        # per-call tensors (allocated 256-byte aligned) and the optional workspaces stand in as OFFERED; the two-pass
+        # log is not offered to very large batches or with little free memory (the block solver needs no log), U Sigma
+        # rebuilt from the transposed cores not when TRANSPOSED_MIX_GRAD is off.
+        OFFERED = 256
+        a.mu_s = a.a_prime = OFFERED
+        a.k_prime = OFFERED if need_bwd else None
+        a.dx = OFFERED if want_dx else None
+        a.raw = OFFERED if need_mix_grad else None
+        a.uw_ce = OFFERED if want_uw else None
+        a.w_stack = OFFERED if need_mix_grad and need_bwd and TRANSPOSED_MIX_GRAD else None
+        jac_bytes = _lib.query("basd_jacobi_twopass_workspace_bytes", n, EB, MAX_SWEEPS) if TWO_PASS_SVD else 0
+        if jac_bytes > TWO_PASS_LOG_LIMIT or (jac_bytes > (256 << 20)
+                                              and jac_bytes > torch.cuda.mem_get_info(dev)[0] // 2):
+            jac_bytes = 0
+        a.jac_ws = OFFERED if jac_bytes > 0 else None
+        route = self.route = self.query_routes()
+        assert route["w_borrow_floats"] <= self.W.numel()
+        # A plan with a mixing-weight gradient serves one call, under the hooks of that call: it holds what its routes
+        # take.  The others are cached and outlive a change of the (process-wide) hooks: of ``route`` they use only what
+        # no hook changes -- tr_part_floats, w_borrow_floats -- and keep the log whenever it is offered, so that the
+        # stacked cores find it under any setting.
+        keep_log = jac_bytes > 0 and (route["svd"] == self.TWO_PASS or not need_mix_grad)
+        self.jac_ws = torch.empty((jac_bytes // 8 + 1,), device=dev, dtype=torch.int64) if keep_log else None
+        # gradients through the mixing weights read U Sigma (the top half of the stacked cores): where the forward takes
+        # the transposed route (cores the plain LDS solver holds), it is rebuilt into this buffer
+        self.w_stack = torch.empty((EB, n, 2 * n), **f32) if route["rebuild_usigma"] else None
+        self.sigma_u = torch.empty((EB, n), **f32) if route["rebuild_usigma"] else None
+        sizes = [GB * n, GB * d_t, route["tr_part_floats"], EB * n]
+        padded = [(c + 63) // 64 * 64 for c in sizes]
+        self.omega_t, self.mu_t, self.tr_part, self.sigma = (
+            piece[:c] for piece, c in zip(torch.split(torch.empty((sum(padded),), **f32), padded), sizes))
         if self.atp:
             a.atap0, a.atap1, a.alam = self.atp.tap0.data_ptr(), self.atp.tap1.data_ptr(), self.atp.lam.data_ptr()
         if self.tp:
@@ -683,8 +716,6 @@ class _ProcrustesPlan:
         a.g_all, a.l_all, a.W = self.g_all.data_ptr(), self.l_all.data_ptr(), self.W.data_ptr()
         a.sigma, a.jflags, a.sweeps = self.sigma.data_ptr(), self.ints.data_ptr(), _ptr(self.sweeps)
         a.h = _ptr(self.h)
-        a.g_slabs = self.g_all[EB + GB:].data_ptr() if g_splits > 1 else None
-        a.g_splits = g_splits
         a.jac_ws = _ptr(self.jac_ws)
         a.w_stack = _ptr(self.w_stack)
         a.sigma_u = _ptr(self.sigma_u)
@@ -722,13 +753,17 @@ def procrustes_forward(students: list[torch.Tensor], teachers: list[torch.Tensor
     need_bwd = need_backward or grad_layers is not None
     want_dx = grad_layers is not None or uwso_ce is not None
     stream = _stream()
-    # mixing-weight gradients read the call's scratch in backward (W, sigma, tc, Grams): those calls get private scratch
+    # what the routes depend on besides the shapes: element types, strides, 16-byte alignment of the student layers
+    s_layout = (_dtype_code(s0), s0.stride(0), s0.stride(1), int(all(s.data_ptr() % 16 == 0 for s in students)))
+    t_layout = (_dtype_code(t0), *t0.stride())
+    # mixing-weight gradients read the call's scratch in backward (W, sigma, tc, Grams): those calls get private scratch,
+    # planned per call (under the hooks of that call)
     key = (E, L, B, n_s, d_s, n_t, d_t, H, A, bool(has_cls), need_bwd, need_mix_grad, want_sweeps, want_dx,
-           uwso_ce is not None, dev, stream, TWO_PASS_SVD)
+           uwso_ce is not None, dev, stream, TWO_PASS_SVD, s_layout, t_layout)
     plan = None if need_mix_grad else _PROCRUSTES_PLANS.get(key)
     if plan is None:
         plan = _ProcrustesPlan(E, L, B, n_s, d_s, n_t, d_t, H, A, has_cls, need_bwd, need_mix_grad, want_sweeps, want_dx,
-                               uwso_ce is not None, dev)
+                               uwso_ce is not None, s_layout, t_layout, dev)
         if not need_mix_grad:
             if len(_PROCRUSTES_PLANS) >= 8:
                 torch.cuda.synchronize(dev)
@@ -758,11 +793,7 @@ def procrustes_forward(students: list[torch.Tensor], teachers: list[torch.Tensor
     for e, s in enumerate(students):
         plan.host_ptrs[e] = s.data_ptr()
     args.student_ptrs = _ptr_table(students).data_ptr()
-    args.s_dtype, args.s_sb, args.s_sn = _dtype_code(s0), s0.stride(0), s0.stride(1)
-    args.s_aligned = int(all(s.data_ptr() % 16 == 0 for s in students))
     args.tok_ptrs = _ptr_table(teachers).data_ptr()
-    args.t_dtype = _dtype_code(t0)
-    args.t_sb, args.t_sn, args.t_sd = t0.stride()
     args.attn_ptrs = _ptr_table(attns).data_ptr()
     args.a_dtype = _dtype_code(a0)
     args.a_sb, args.a_sh, args.a_sq, args.a_sk = a0.stride()
@@ -779,10 +810,12 @@ def procrustes_forward(students: list[torch.Tensor], teachers: list[torch.Tensor
     mixgrad = None
     if need_mix_grad:
         l_a, g_b = plan.l_all[:EB], plan.g_all[EB:EB + G * B]
-        mixgrad = dict(raw=raw, tc=plan.tc, l_a=l_a, g_b=g_b, W=plan.w_stack if plan.w_stack is not None else plan.W,
-                       sigma=plan.sigma_u if plan.w_stack is not None else plan.sigma, omega_e=omega,
+        in_w_stack = plan.route["usigma_in"] == plan.IN_W_STACK
+        mixgrad = dict(raw=raw, tc=plan.tc, l_a=l_a, g_b=g_b, W=plan.w_stack if in_w_stack else plan.W,
+                       sigma=plan.sigma_u if in_w_stack else plan.sigma, omega_e=omega,
                        teachers=teachers, attns=attns, tok_tab=_ptr_table(teachers), att_tab=_ptr_table(attns),
-                       has_cls=has_cls, n_a=n_a, n=n, n_s=n_s, gather=plan.gt, student_taps=plan.tp, attn_taps=plan.atp)
+                       has_cls=has_cls, n_a=n_a, n=n, n_s=n_s, gather=plan.gt, student_taps=plan.tp, attn_taps=plan.atp,
+                       route=plan.route)
     sweeps = plan.sweeps.clone() if plan.sweeps is not None else None
     return ProcrustesContext(omega, mu_s, a_prime, k_prime, terms[0], terms[1], terms[2], terms[3], sweeps, mixgrad,
                              dx, uw)

@@ -17,6 +17,13 @@
         if (!(cond)) return BASD_EINVAL; \
     } while (0)
 
+// Pass a failed status of a nested library call on to the caller.
+#define BASD_TRY(call)                \
+    do {                              \
+        int rc_ = (call);             \
+        if (rc_ != BASD_OK) return rc_; \
+    } while (0)
+
 // Kernel launches never throw; a HIP error is returned as a positive status.
 #define BASD_RETURN_LAST()                         \
     do {                                           \

@@ -135,11 +135,6 @@ __global__ void __launch_bounds__(256) debug_fill_lds_kernel(unsigned pattern, i
 
 }  // namespace basd
 
-#define BASD_TRY(call)                \
-    do {                              \
-        int rc_ = (call);             \
-        if (rc_ != BASD_OK) return rc_; \
-    } while (0)
 #define BASD_HIP(call)                          \
     do {                                        \
         hipError_t e_ = (call);                 \

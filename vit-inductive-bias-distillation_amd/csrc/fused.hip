@@ -3,7 +3,7 @@
 // Python cost several times the launches themselves and that host time sits in front of the kernels of the caller's
 // stream (round-1 timeline: the first Procrustes kernel started 1.05 ms into a 3.5 ms step).
 #include "basd_common.h"
-#include "../../include/basd_hip.h"
+#include "procrustes_plan.h"
 
 namespace basd {
 
@@ -72,38 +72,6 @@ int basd_scale_unless_one(float* x, long count, const float* num, const float* d
     BASD_RETURN_LAST();
 }
 
-// combined.py:76-85 and the student gradients: the end of basd_procrustes_forward_fused, shared by its two SVD routes.
-static int procrustes_tail(const BasdProcrustesArgs* a, const float* grad_layers, int E, int B, int n_s, int n, int d_s,
-                           int EB, long nn, long om_stride, hipStream_t st) {
-    int rc;
-#define BASD_TRY(call)            \
-    do {                          \
-        rc = (call);              \
-        if (rc != BASD_OK) return rc; \
-    } while (0)
-    // combined.py:76-85: the UW-SO weights and the total, on the device (the student gradients below are then final)
-    if (a->uw_ce) {
-        BASD_CHECK_ARG(a->uw_out != nullptr);
-        basd::uwso_combine_kernel<<<1, 256, 0, st>>>(a->uw_ce, a->loss_b, E, B, a->uw_out);
-        grad_layers = a->uw_out + 4;
-    }
-    // student gradients for the upstream gradients grad_layers (E floats on the device): H = K' A', then one pass
-    if (a->dx) {
-        BASD_CHECK_ARG(a->k_prime && a->h && grad_layers);
-        rc = basd_student_grad_fused(a->student_ptrs, (int)a->s_dtype, a->s_sb, a->s_sn, E, B, n_s, n, d_s,
-                                     (int)a->s_aligned, a->omega, om_stride, a->mu_s, a->k_prime, a->a_prime, a->tap0,
-                                     a->tap1, a->lam, grad_layers, 2.0f / (float)B, a->dx, st);
-        if (rc != BASD_EUNSUPPORTED) return rc;
-        BASD_TRY(basd_gemm_tn(a->k_prime, a->a_prime, BASD_DTYPE_F32, 0, n, 1, nn, 0, d_s, 1, (long)n * d_s, 1 << 30, n,
-                              n, d_s, EB, nullptr, nullptr, 1, nullptr, a->h, d_s, (long)n * d_s, 1.f, st));
-        BASD_TRY(basd_student_grad_multi(a->student_ptrs, (int)a->s_dtype, a->s_sb, a->s_sn, E, B, n_s, n, d_s, a->omega,
-                                         om_stride, a->mu_s, a->h, a->tap0, a->tap1, a->lam, grad_layers,
-                                         2.0f / (float)B, a->dx, nullptr, nullptr, st));
-    }
-#undef BASD_TRY
-    return BASD_OK;
-}
-
 // Test hook: 0 keeps the stacked cores [M; L_b] (riding rows) for every shape, 2 drops the batch threshold.
 static int g_transposed_cores = 1;
 int basd_procrustes_tuning(int transposed_cores) {
@@ -119,124 +87,144 @@ int basd_procrustes_finish_tuning(int fused) {
     return prev;
 }
 
+// What basd_procrustes_forward_fused would launch for these arguments under the current hooks (host only, no HIP call;
+// pointers are only tested for presence and alignment): the fields of basd::plan::ProcrustesPlan in order.
+int basd_procrustes_plan_query(const BasdProcrustesArgs* a, long* out20) {
+    using namespace basd::plan;
+    BASD_CHECK_ARG(out20);
+    ProcrustesPlan p;
+    BASD_TRY(procrustes_plan(a, g_transposed_cores, g_finish_fused, &p));
+    const long out[kPlanFields] = {p.center, p.project, p.slab_width, p.slabs, p.gram_split, p.chol, p.cores,
+                                   p.svd, p.finish, p.rebuild_usigma, p.grad, p.usigma_in, p.tr_part_floats,
+                                   p.w_borrow_floats, p.lds_center, p.lds_project, p.lds_gram, p.lds_chol,
+                                   p.lds_finish, p.lds_grad};
+    for (int i = 0; i < kPlanFields; ++i) out20[i] = out[i];
+    return p.status();
+}
+
 // relational.py:22-50 for all extraction layers against the (mixed) teacher, forward and -- optionally -- the student
-// gradients for given upstream gradients; see BasdProcrustesArgs in include/basd_hip.h.
+// gradients for given upstream gradients; see BasdProcrustesArgs in include/basd_hip.h.  The routes are those of the
+// plan: where it names one of several entry points, that one is called and a refusal is returned as the error it is,
+// never answered with another route.  The stages with a single entry point (Grams, Cholesky, finalize) are simply
+// called: past their bounds they refuse for themselves, from the predicates the plan's status is made of, and the
+// call ends there as it does at a stage without a route.
 int basd_procrustes_forward_fused(const BasdProcrustesArgs* a, hipStream_t st) {
+    using namespace basd::plan;
     BASD_CHECK_ARG(a && a->student_ptrs && a->tok_ptrs && a->attn_ptrs && a->mix);
-    const int E = (int)a->E, L = (int)a->L, G = (int)a->G, B = (int)a->B, n_s = (int)a->n_s, n_t = (int)a->n_t;
+    ProcrustesPlan p;
+    BASD_TRY(procrustes_plan(a, g_transposed_cores, g_finish_fused, &p));
+    const int E = (int)a->E, L = (int)a->L, G = (int)a->G, B = (int)a->B, n_s = (int)a->n_s;
     const int d_s = (int)a->d_s, d_t = (int)a->d_t, H = (int)a->H, A = (int)a->A, n_a = (int)a->n_a, n = (int)a->n;
-    const float* grad_layers_in = a->grad_layers;
-    BASD_CHECK_ARG(E > 0 && L > 0 && (G == 1 || G == E) && B > 0 && n == (n_s < n_t ? n_s : n_t));
-    int rc;
-#define BASD_TRY(call)            \
-    do {                          \
-        rc = (call);              \
-        if (rc != BASD_OK) return rc; \
-    } while (0)
+    const int td = (int)a->t_dtype, sd = (int)a->s_dtype;
     // teacher side: token weights + mixed, centred teacher, once per group (G = 1: shared by all layers)
-    int centred = BASD_EUNSUPPORTED;
     for (int g = 0; g < G; ++g) {
         BASD_TRY(basd_token_weights(a->attn_ptrs, (int)a->a_dtype, a->mix + (long)g * L, L, a->a_sb, a->a_sh, a->a_sq,
                                     a->a_sk, B, H, A, (int)a->has_cls, n_a, n, n_s, a->atap0, a->atap1, a->alam,
                                     a->tap0, a->tap1, a->lam, a->omega + (long)g * B * n_s,
                                     a->omega_t + (long)g * B * n, a->raw ? a->raw + (long)g * B * n_a : nullptr, st));
     }
-    // mixed, centred teacher: all groups in one pass over the teacher layers where that applies
-    if (G > 1 && L >= 4 && basd_teacher_center_stream_scratch_floats(G, B, n, d_t) <= (long)E * B * 2 * n * n) {
-        // many layers: the streaming form; its per-chunk column sums borrow W, which is not written before the stacked
-        // product
-        centred = basd_teacher_center_stream(a->tok_ptrs, (int)a->t_dtype, a->mix, L, G, a->t_sb, a->t_sn, a->t_sd, B, n,
-                                             d_t, a->g0, a->g1, a->glam, a->omega_t, a->mu_t, a->tc, a->W, st);
-        if (centred != BASD_OK && centred != BASD_EUNSUPPORTED) return centred;
+    switch (p.center) {
+        case kCenterStreamV4:
+        case kCenterStream:     // its per-chunk column sums borrow W, which is not written before the stacked product
+            BASD_TRY(basd_teacher_center_stream(a->tok_ptrs, td, a->mix, L, G, a->t_sb, a->t_sn, a->t_sd, B, n, d_t, a->g0,
+                                                a->g1, a->glam, a->omega_t, a->mu_t, a->tc, a->W, st));
+            break;
+        case kCenterMulti:
+            BASD_TRY(basd_teacher_center_multi(a->tok_ptrs, td, a->mix, L, G, a->t_sb, a->t_sn, a->t_sd, B, n, d_t, a->g0,
+                                               a->g1, a->glam, a->omega_t, a->mu_t, a->tc, st));
+            break;
+        case kCenterPerGroup:
+            for (int g = 0; g < G; ++g)
+                BASD_TRY(basd_teacher_center(a->tok_ptrs, td, a->mix + (long)g * L, L, a->t_sb, a->t_sn, a->t_sd, B, n, d_t,
+                                             a->g0, a->g1, a->glam, a->omega_t + (long)g * B * n,
+                                             a->mu_t + (long)g * B * d_t, a->tc + (long)g * B * n * d_t, st));
+            break;
+        default:
+            return BASD_EUNSUPPORTED;
     }
-    if (G > 1 && centred != BASD_OK) {
-        centred = basd_teacher_center_multi(a->tok_ptrs, (int)a->t_dtype, a->mix, L, G, a->t_sb, a->t_sn, a->t_sd, B, n,
-                                            d_t, a->g0, a->g1, a->glam, a->omega_t, a->mu_t, a->tc, st);
-        if (centred != BASD_OK && centred != BASD_EUNSUPPORTED) return centred;
-    }
-    for (int g = 0; g < G && centred != BASD_OK; ++g) {
-        BASD_TRY(basd_teacher_center(a->tok_ptrs, (int)a->t_dtype, a->mix + (long)g * L, L, a->t_sb, a->t_sn, a->t_sd,
-                                     B, n, d_t, a->g0, a->g1, a->glam, a->omega_t + (long)g * B * n,
-                                     a->mu_t + (long)g * B * d_t, a->tc + (long)g * B * n * d_t, st));
-    }
-    // student side: all layers in one launch where the vectorised kernel applies
+    // student side
     const long om_stride = G == 1 ? 0 : (long)B * n_s;
-    int slabs = (d_s + 31) / 32;          // partial traces per sample: 32-feature slabs (multi) or 64 (per layer)
-    rc = basd_student_project_multi(a->student_ptrs, (int)a->s_dtype, a->s_sb, a->s_sn, E, B, n_s, n, d_s,
-                                    (int)a->s_aligned, a->omega, om_stride, a->tap0, a->tap1, a->lam, a->range0,
-                                    a->range1, a->mu_s, a->tr_part, a->a_prime, st);
-    if (rc == BASD_EUNSUPPORTED) {
-        slabs = (d_s + 63) / 64;
+    if (p.project == kProjectNone) return p.status();
+    if (p.project == kProjectMulti) {
+        BASD_TRY(basd_student_project_multi(a->student_ptrs, sd, a->s_sb, a->s_sn, E, B, n_s, n, d_s, (int)a->s_aligned,
+                                            a->omega, om_stride, a->tap0, a->tap1, a->lam, a->range0, a->range1, a->mu_s,
+                                            a->tr_part, a->a_prime, st));
+    } else {
         for (int e = 0; e < E; ++e)
-            BASD_TRY(basd_student_project(a->student_host_ptrs[e], (int)a->s_dtype, a->s_sb, a->s_sn, B, n_s, n, d_s,
+            BASD_TRY(basd_student_project(a->student_host_ptrs[e], sd, a->s_sb, a->s_sn, B, n_s, n, d_s,
                                           a->omega + e * om_stride, a->tap0, a->tap1, a->lam, a->range0, a->range1,
-                                          a->mu_s + (long)e * B * d_s, a->tr_part + (long)e * B * slabs,
+                                          a->mu_s + (long)e * B * d_s, a->tr_part + (long)e * B * p.slabs,
                                           a->a_prime + (long)e * B * n * d_s, st));
-    } else if (rc != BASD_OK) {
-        return rc;
     }
-    // fp64 Grams on the core grid, Cholesky factors, stacked product, SVD, per-sample terms
+    // fp64 Grams on the core grid, Cholesky factors, product, SVD, per-sample terms
     const long nn = (long)n * n;
     const int EB = E * B, GB = G * B;
+    double* g_b = a->g_all + (long)EB * nn;
+    double* l_b = a->l_all + (long)EB * nn;
     BASD_TRY(basd_gram_f64(a->a_prime, (long)n * d_s, n, d_s, EB, a->g_all, nn, st));
-    if (a->g_slabs && a->g_splits > 1)
-        BASD_TRY(basd_gram_f64_split(a->tc, (long)n * d_t, n, d_t, GB, (int)a->g_splits, a->g_slabs,
-                                     a->g_all + (long)EB * nn, st));
+    if (p.gram_split)
+        BASD_TRY(basd_gram_f64_split(a->tc, (long)n * d_t, n, d_t, GB, (int)a->g_splits, a->g_slabs, g_b, st));
     else
-        BASD_TRY(basd_gram_f64(a->tc, (long)n * d_t, n, d_t, GB, a->g_all + (long)EB * nn, nn, st));
+        BASD_TRY(basd_gram_f64(a->tc, (long)n * d_t, n, d_t, GB, g_b, nn, st));
     BASD_TRY(basd_chol_f64(a->g_all, nn, n, EB + GB, a->l_all, nn, st));
-    // Cores that the plain 4-lane LDS solver takes, when nothing needs U Sigma afterwards (no gradient through the
-    // mixing weights): the Jacobi runs on M^T alone -- its columns come out as V Sigma -- and Y = L_b V is formed when K'
-    // is (half the rows per pair-step, no two-pass / block solver at cfg-5's 144 tokens).
-    // With gradients through the mixing weights (a->raw set) the backward reads U Sigma, the top half of the stacked
-    // cores: it is rebuilt from the transposed route's Z afterwards (a->w_stack), so those steps take this route too.
-    if ((a->raw == nullptr || a->w_stack != nullptr) && EB <= 65535 && basd_jacobi_plain4_fits(n) &&
-        (g_transposed_cores == 2 || (g_transposed_cores == 1 && EB >= 128))) {
-        BASD_TRY(basd_stack_product_t(a->l_all, a->l_all + (long)EB * nn, nn, n, EB, GB, a->W, 2 * nn, st));
-        if (a->raw != nullptr) BASD_TRY(basd_ustack_stash(a->W, 2 * nn, n, EB, a->w_stack, 2 * nn, st));
+    if (p.cores == kCoresTransposed) {
+        BASD_TRY(basd_stack_product_t(a->l_all, l_b, nn, n, EB, GB, a->W, 2 * nn, st));
+        if (p.rebuild_usigma) BASD_TRY(basd_ustack_stash(a->W, 2 * nn, n, EB, a->w_stack, 2 * nn, st));
         BASD_TRY(basd_jacobi_onesided(a->W, 2 * nn, n, n, n, EB, nullptr, a->sigma, n, (int)a->max_sweeps, 0.f,
                                       a->jflags, a->sweeps, st));
-        // cores of up to 64 tokens: the per-sample terms and K' in one launch, same bits (see the kernel)
-        rc = BASD_EUNSUPPORTED;
-        if (a->k_prime && g_finish_fused)
-            rc = basd_procrustes_finish_transposed(a->W, 2 * nn, a->sigma, n, n_s, EB, GB, a->g_all + (long)EB * nn, nn,
-                                                   a->omega, a->tap0, a->tap1, a->lam, a->tr_part, slabs, a->tr_s,
-                                                   a->tr_t, a->nuc, a->loss_b, a->l_all + (long)EB * nn, nn, GB,
-                                                   a->k_prime, st);
-        if (rc == BASD_EUNSUPPORTED) {
-            BASD_TRY(basd_procrustes_finalize(a->W, 2 * nn, a->sigma, n, n_s, EB, GB, a->g_all + (long)EB * nn, nn,
-                                              a->omega, a->tap0, a->tap1, a->lam, a->tr_part, slabs, a->tr_s, a->tr_t,
-                                              a->nuc, a->loss_b, nullptr, st));
-            if (a->k_prime)
-                BASD_TRY(basd_kprime_from_transposed(a->W, 2 * nn, a->sigma, n, EB, a->l_all + (long)EB * nn, nn, GB,
-                                                     a->W + nn, 2 * nn, a->k_prime, st));
-        } else if (rc != BASD_OK) {
-            return rc;
-        }
-        if (a->raw != nullptr) {
-            BASD_CHECK_ARG(a->sigma_u != nullptr);
-            // (scratch: the z region behind X, free again once K' has been formed)
-            BASD_TRY(basd_ustack_from_transposed(a->W, 2 * nn, a->sigma, n, EB, a->w_stack, 2 * nn, a->W + nn, 2 * nn,
-                                                 a->sigma_u, (int)a->max_sweeps, a->jflags, st));
-        }
-        return procrustes_tail(a, grad_layers_in, E, B, n_s, n, d_s, EB, nn, om_stride, st);
+    } else {
+        BASD_TRY(basd_stack_product(a->l_all, l_b, nn, n, EB, GB, a->W, 2 * nn, st));
+        int rc = BASD_EUNSUPPORTED;
+        if (p.svd == kSvdTwoPass)       // the one route that is tried: see Svd
+            rc = basd_jacobi_stacked_twopass(a->W, 2 * nn, n, EB, a->sigma, n, (int)a->max_sweeps, 0.f, a->jac_ws,
+                                             a->sweeps, st);
+        if (rc == BASD_EUNSUPPORTED)
+            rc = basd_jacobi_onesided(a->W, 2 * nn, n, 2 * n, n, EB, nullptr, a->sigma, n, (int)a->max_sweeps, 0.f,
+                                      a->jflags, a->sweeps, st);
+        if (rc != BASD_OK) return rc;
     }
-    BASD_TRY(basd_stack_product(a->l_all, a->l_all + (long)EB * nn, nn, n, EB, GB, a->W, 2 * nn, st));
-    rc = BASD_EUNSUPPORTED;
-    if (a->jac_ws)
-        rc = basd_jacobi_stacked_twopass(a->W, 2 * nn, n, EB, a->sigma, n, (int)a->max_sweeps, 0.f, a->jac_ws, a->sweeps,
-                                         st);
-    if (rc == BASD_EUNSUPPORTED)
-        rc = basd_jacobi_onesided(a->W, 2 * nn, n, 2 * n, n, EB, nullptr, a->sigma, n, (int)a->max_sweeps, 0.f,
-                                  a->jflags, a->sweeps, st);
-    if (rc != BASD_OK) return rc;
-    BASD_TRY(basd_procrustes_finalize(a->W, 2 * nn, a->sigma, n, n_s, EB, GB, a->g_all + (long)EB * nn, nn, a->omega,
-                                      a->tap0, a->tap1, a->lam, a->tr_part, slabs, a->tr_s, a->tr_t, a->nuc,
-                                      a->loss_b, a->k_prime, st));
-    return procrustes_tail(a, grad_layers_in, E, B, n_s, n, d_s, EB, nn, om_stride, st);
-#undef BASD_TRY
+    if (p.finish == kFinishTransposed) {
+        // cores of up to 64 tokens: the per-sample terms and K' in one launch, same bits (see the kernel)
+        BASD_TRY(basd_procrustes_finish_transposed(a->W, 2 * nn, a->sigma, n, n_s, EB, GB, g_b, nn, a->omega, a->tap0,
+                                                   a->tap1, a->lam, a->tr_part, p.slabs, a->tr_s, a->tr_t, a->nuc,
+                                                   a->loss_b, l_b, nn, GB, a->k_prime, st));
+    } else {
+        // behind the transposed cores K' = Y Sigma^+ Y^T needs Y = L_b V first: not in finalize's reach
+        BASD_TRY(basd_procrustes_finalize(a->W, 2 * nn, a->sigma, n, n_s, EB, GB, g_b, nn, a->omega, a->tap0, a->tap1,
+                                          a->lam, a->tr_part, p.slabs, a->tr_s, a->tr_t, a->nuc, a->loss_b,
+                                          p.cores == kCoresTransposed ? nullptr : a->k_prime, st));
+        if (p.finish == kFinalizeKprimeT)
+            BASD_TRY(basd_kprime_from_transposed(a->W, 2 * nn, a->sigma, n, EB, l_b, nn, GB, a->W + nn, 2 * nn,
+                                                 a->k_prime, st));
+    }
+    if (p.rebuild_usigma) {
+        BASD_CHECK_ARG(a->sigma_u != nullptr);
+        // (scratch: the z region behind X, free again once K' has been formed)
+        BASD_TRY(basd_ustack_from_transposed(a->W, 2 * nn, a->sigma, n, EB, a->w_stack, 2 * nn, a->W + nn, 2 * nn,
+                                             a->sigma_u, (int)a->max_sweeps, a->jflags, st));
+    }
+    // combined.py:76-85: the UW-SO weights and the total, on the device (the student gradients below are then final)
+    const float* grad_layers = a->grad_layers;
+    if (a->uw_ce) {
+        BASD_CHECK_ARG(a->uw_out != nullptr);
+        basd::uwso_combine_kernel<<<1, 256, 0, st>>>(a->uw_ce, a->loss_b, E, B, a->uw_out);
+        grad_layers = a->uw_out + 4;
+    }
+    // student gradients for the upstream gradients grad_layers (E floats on the device): H = K' A', then one pass
+    if (p.grad != kGradNone) BASD_CHECK_ARG(a->k_prime && a->h && grad_layers);
+    if (p.grad == kGradFused) {
+        BASD_TRY(basd_student_grad_fused(a->student_ptrs, sd, a->s_sb, a->s_sn, E, B, n_s, n, d_s, (int)a->s_aligned,
+                                         a->omega, om_stride, a->mu_s, a->k_prime, a->a_prime, a->tap0, a->tap1, a->lam,
+                                         grad_layers, 2.0f / (float)B, a->dx, st));
+    } else if (p.grad == kGradGemmMulti) {
+        BASD_TRY(basd_gemm_tn(a->k_prime, a->a_prime, BASD_DTYPE_F32, 0, n, 1, nn, 0, d_s, 1, (long)n * d_s, 1 << 30, n,
+                              n, d_s, EB, nullptr, nullptr, 1, nullptr, a->h, d_s, (long)n * d_s, 1.f, st));
+        BASD_TRY(basd_student_grad_multi(a->student_ptrs, sd, a->s_sb, a->s_sn, E, B, n_s, n, d_s, a->omega, om_stride,
+                                         a->mu_s, a->h, a->tap0, a->tap1, a->lam, grad_layers, 2.0f / (float)B, a->dx,
+                                         nullptr, nullptr, st));
+    }
+    return BASD_OK;
 }
-
 
 // Events for ordering two streams from inside a library call (see basd_tridiag_ranked's mid_event).
 int basd_event_create(void** out) {

@@ -17,7 +17,7 @@
 //   d nuc / d A' = K' A',   K' = Y Sigma^+ Y^T   (n x n, symmetric PSD)
 // which the finalize kernel emits; the student-token gradient is then a streaming pass.
 #include "basd_common.h"
-#include "../../include/basd_hip.h"
+#include "procrustes_plan.h"
 
 namespace basd {
 
@@ -174,10 +174,7 @@ __global__ void __launch_bounds__(256) student_project_kernel(const T* __restric
     }
 }
 
-// Same, with the workgroup's (n_s x 64) slab of X staged in LDS by one coalesced pass (16-byte loads): the three
-// sweeps (weighted mean, trace, projection) then read LDS instead of pulling 256-byte row segments through L2
-// four or five times.  Needs 16-byte aligned rows and (n_s * 65) floats of LDS (n_s <= ~600).
-__device__ __forceinline__ float4 ld4f(const float* p) { return *(const float4*)p; }
+// 16-byte loads of four features (fp32, or bf16 widened) through a pointer into global memory
 typedef float native_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned native_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float4 ld4f(const BASD_GLOBAL_AS float* p) {
@@ -189,75 +186,6 @@ __device__ __forceinline__ float4 ld4f(const BASD_GLOBAL_AS __hip_bfloat16* p) {
     return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
                        __uint_as_float(v.y & 0xffff0000u));
 }
-__device__ __forceinline__ float4 ld4f(const __hip_bfloat16* p) {
-    const uint2 v = *(const uint2*)p;
-    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
-                       __uint_as_float(v.y & 0xffff0000u));
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256) student_project_lds_kernel(const T* __restrict__ X, long sb, long sn, int n_s,
-                                                                  int n_t, int D, const float* __restrict__ omega,
-                                                                  const int* __restrict__ tap0,
-                                                                  const int* __restrict__ tap1,
-                                                                  const float* __restrict__ lam,
-                                                                  const int* __restrict__ range0,
-                                                                  const int* __restrict__ range1,
-                                                                  float* __restrict__ mu_out,
-                                                                  float* __restrict__ tr_part, float* __restrict__ Ap) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* xs = sm;                      // n_s x 64 slab, row-major
-    float* w = sm + (long)n_s * 64;      // n_s
-    __shared__ float red[4][64];
-    __shared__ float mu[64];
-    __shared__ float scratch[32];
-    const int b = blockIdx.y, d0 = blockIdx.x * 64, tid = threadIdx.x;
-    const int cl = tid & 63, rg = tid >> 6, d = d0 + cl;
-    const bool live = d < D;
-    const T* Xb = X + (long)b * sb + d0;
-    for (int n = tid; n < n_s; n += 256) w[n] = omega[(long)b * n_s + n];
-    for (int idx = tid; idx < n_s * 16; idx += 256) {
-        const int row = idx >> 4, c4 = (idx & 15) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (d0 + c4 < D) v = ld4f(Xb + (long)row * sn + c4);        // D % 4 == 0: the quad is inside or outside
-        *(float4*)(xs + row * 64 + c4) = v;
-    }
-    __syncthreads();
-    float acc = 0.f;
-    for (int n = rg; n < n_s; n += 4) acc = fmaf(w[n], xs[n * 64 + cl], acc);
-    red[rg][cl] = acc;
-    __syncthreads();
-    if (rg == 0) {
-        const float m = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
-        mu[cl] = m;
-        if (live) mu_out[(long)b * D + d] = m;
-    }
-    __syncthreads();
-    const float m = mu[cl];
-    float part = 0.f;
-    if (live)
-        for (int n = rg; n < n_s; n += 4) {
-            const float c = xs[n * 64 + cl] - m;
-            part = fmaf(w[n] * c, c, part);
-        }
-    const float tr = block_sum(part, scratch);
-    if (tid == 0) tr_part[(long)b * gridDim.x + blockIdx.x] = tr;
-    if (!live) return;
-    float* Ab = Ap + (long)b * n_t * D + d;
-    for (int j = rg; j < n_t; j += 4) {
-        const int n0 = range0 ? range0[j] : j, n1 = range1 ? range1[j] : j + 1;
-        float a = 0.f;
-        for (int n = n0; n < n1; ++n) {
-            float coef = 1.f;
-            if (tap0) {
-                const float l1 = lam[n];
-                coef = (tap0[n] == j ? 1.f - l1 : 0.f) + (tap1[n] == j ? l1 : 0.f);
-            }
-            a = fmaf(coef * w[n], xs[n * 64 + cl] - m, a);
-        }
-        Ab[(long)j * D] = a;
-    }
-}
 
 // All E extraction layers in ONE launch, 16-byte LDS accesses.  grid = (ceil(D/32), B, E), block = 256 =
 // 8 feature quads x 32 row groups.  The (n_s x 32) slab (128-byte rows, contiguous in LDS) is staged once by
@@ -267,7 +195,6 @@ __global__ void __launch_bounds__(256) student_project_lds_kernel(const T* __res
 // traffic, bound by LDS issue), and the interpolation coefficients sit in LDS too (they used to be three dependent
 // global loads per row of the projection loop).  27 KB of LDS per workgroup at n_s = 196: five workgroups per CU.
 // x_ptrs: device table of E base pointers (same strides); omega + e * omega_e_stride; outputs are (E, B, ...).
-constexpr int SP_W = 32;          // slab width in features
 template <typename T>
 __global__ void __launch_bounds__(256) student_project_v4_kernel(const void* const* __restrict__ x_ptrs, long sb,
                                                                  long sn, int n_s, int n_t, int D,
@@ -424,7 +351,6 @@ __global__ void __launch_bounds__(256) teacher_center_kernel(const void* const* 
 // The same for G <= 4 groups of mixing weights in ONE pass over the teacher layers (multi-layer teachers: one group per
 // extraction layer; the per-group kernel read all L layers once per group -- 4 x 2.5 GB per step at cfg-4).  Slabs of 16
 // features so that the G tiles fit LDS together.  omega_t (G, B, n), mu_out (G, B, D), Tc (G, B, n, D).
-constexpr int TCM_W = 16, TCM_G = 4;
 template <typename T>
 __global__ void __launch_bounds__(256) teacher_center_multi_kernel(
     const void* const* __restrict__ tok_ptrs, const float* __restrict__ mix, int L, int G, long sb, long sn, long sd,
@@ -496,7 +422,6 @@ __global__ void __launch_bounds__(256) teacher_center_multi_kernel(
 // in a fixed order into the weighted mean and subtracts it in place.  2.5 GB read once + 0.4 GB written + 0.8 GB for
 // the centring pass at cfg-4, against 64-byte row segments through a 16-feature LDS tile in the kernel above.
 // pass 1: grid = (chunks, B), block = 256.  pass 2: grid = (ceil(D / 256), chunks, G * B), block = 256.
-constexpr int TCS_ROWS = 16;
 template <typename T>
 __global__ void __launch_bounds__(256) teacher_mix_stream_kernel(
     const void* const* __restrict__ tok_ptrs, const float* __restrict__ mix, int L, int G, long sb, long sn, long sd, int n,
@@ -536,6 +461,91 @@ __global__ void __launch_bounds__(256) teacher_mix_stream_kernel(
     }
 }
 
+// The same for fp32 tokens on the teacher's own grid with 16-byte aligned rows (ViT teachers: cfg-4): a thread owns FOUR
+// consecutive features, the layers are read four at a time with all loads in flight before the first use (the scalar form
+// issues one 4-byte load per layer and waits for it: 2.5 TB/s over 24 layers of 103 MB).  Falls back to the scalar form
+// inside the launch when a layer's base pointer is not 16-byte aligned (wave-uniform).
+__global__ void __launch_bounds__(256) teacher_mix_stream_v4_kernel(
+    const void* const* __restrict__ tok_ptrs, const float* __restrict__ mix, int L, int G, long sb, long sn, int n, int D,
+    const float* __restrict__ omega_t, float* __restrict__ Tc, float* __restrict__ chunk_sum) {
+    const int chunk = blockIdx.x, b = blockIdx.y, B = gridDim.y, tid = threadIdx.x;
+    const int j_lo = chunk * TCS_ROWS, j_hi = j_lo + TCS_ROWS < n ? j_lo + TCS_ROWS : n;
+    bool aligned = true;
+    for (int l = 0; l < L; ++l) aligned = aligned && (((uintptr_t)tok_ptrs[l]) & 15) == 0;
+    if (!aligned) {       // uniform over the launch
+        for (int d = tid; d < D; d += 256) {
+            float musum[TCM_G] = {0.f, 0.f, 0.f, 0.f};
+            for (int j = j_lo; j < j_hi; ++j) {
+                const long o0 = b * sb + (long)j * sn + d;
+                float v[TCM_G] = {0.f, 0.f, 0.f, 0.f};
+                for (int l = 0; l < L; ++l) {
+                    const float x = ldg_f32((const BASD_GLOBAL_AS float*)tok_ptrs[l] + o0);
+#pragma unroll
+                    for (int g = 0; g < TCM_G; ++g)
+                        if (g < G) v[g] = fmaf(mix[g * L + l], x, v[g]);
+                }
+#pragma unroll
+                for (int g = 0; g < TCM_G; ++g)
+                    if (g < G) {
+                        Tc[(((long)g * B + b) * n + j) * D + d] = v[g];
+                        musum[g] = fmaf(omega_t[((long)g * B + b) * n + j], v[g], musum[g]);
+                    }
+            }
+#pragma unroll
+            for (int g = 0; g < TCM_G; ++g)
+                if (g < G) chunk_sum[(((long)chunk * G + g) * B + b) * D + d] = musum[g];
+        }
+        return;
+    }
+    for (int d = 4 * tid; d < D; d += 1024) {
+        float4 musum[TCM_G];
+#pragma unroll
+        for (int g = 0; g < TCM_G; ++g) musum[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int j = j_lo; j < j_hi; ++j) {
+            const long o0 = b * sb + (long)j * sn + d;
+            float4 v[TCM_G];
+#pragma unroll
+            for (int g = 0; g < TCM_G; ++g) v[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+            int l = 0;
+            for (; l + 4 <= L; l += 4) {
+                float4 x[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) x[q] = ld4f((const BASD_GLOBAL_AS float*)tok_ptrs[l + q] + o0);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int g = 0; g < TCM_G; ++g)
+                        if (g < G) {
+                            const float m = mix[g * L + l + q];
+                            v[g].x = fmaf(m, x[q].x, v[g].x); v[g].y = fmaf(m, x[q].y, v[g].y);
+                            v[g].z = fmaf(m, x[q].z, v[g].z); v[g].w = fmaf(m, x[q].w, v[g].w);
+                        }
+            }
+            for (; l < L; ++l) {
+                const float4 x = ld4f((const BASD_GLOBAL_AS float*)tok_ptrs[l] + o0);
+#pragma unroll
+                for (int g = 0; g < TCM_G; ++g)
+                    if (g < G) {
+                        const float m = mix[g * L + l];
+                        v[g].x = fmaf(m, x.x, v[g].x); v[g].y = fmaf(m, x.y, v[g].y);
+                        v[g].z = fmaf(m, x.z, v[g].z); v[g].w = fmaf(m, x.w, v[g].w);
+                    }
+            }
+#pragma unroll
+            for (int g = 0; g < TCM_G; ++g)
+                if (g < G) {
+                    *(float4*)(Tc + (((long)g * B + b) * n + j) * D + d) = v[g];
+                    const float om = omega_t[((long)g * B + b) * n + j];
+                    musum[g].x = fmaf(om, v[g].x, musum[g].x); musum[g].y = fmaf(om, v[g].y, musum[g].y);
+                    musum[g].z = fmaf(om, v[g].z, musum[g].z); musum[g].w = fmaf(om, v[g].w, musum[g].w);
+                }
+        }
+#pragma unroll
+        for (int g = 0; g < TCM_G; ++g)
+            if (g < G) *(float4*)(chunk_sum + (((long)chunk * G + g) * B + b) * D + d) = musum[g];
+    }
+}
+
 __global__ void __launch_bounds__(256) teacher_center_apply_kernel(const float* __restrict__ chunk_sum, int chunks, int n,
                                                                    int D, float* __restrict__ mu_out,
                                                                    float* __restrict__ Tc) {
@@ -556,7 +566,6 @@ __global__ void __launch_bounds__(256) teacher_center_apply_kernel(const float* 
 // v_mfma_f64_16x16x4_f64: lane l holds A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15];
 // D: col = l & 15, row = (l >> 4) + 4 * reg.
 // ---------------------------------------------------------------------------
-constexpr int G64_BK = 32, G64_LD = 36, G64_TPW = 8;
 
 // blockIdx.y = split s of gridDim.y over the contraction index: the split handles D-chunks s, s + S, ... and writes its
 // partial Gram to G + s * g_split_stride (gram_f64_reduce_kernel folds them in a fixed order).
@@ -661,8 +670,8 @@ static bool gram_f64_shape(int n, int* waves, int* chunks, size_t* lds) {
     }
     *waves = w;
     *chunks = c;
-    *lds = sizeof(float) * (size_t)nt * 16 * G64_LD;
-    if (*lds > 156 * 1024) return false;
+    *lds = plan::gram_lds(n);
+    if (!plan::gram_fits(n)) return false;
     if (*lds > 48 * 1024)
         (void)hipFuncSetAttribute((const void*)gram_f64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     return true;
@@ -732,7 +741,6 @@ __global__ void __launch_bounds__(1024) chol_f64_kernel(const double* __restrict
 // panel -- rows j0..n-1 of CB_NB columns -- is accumulated in registers (thread (row group, column): rows rg + 64 r),
 // parked in LDS and factored there column by column with the pivot rule of chol_f64_kernel.
 // grid = batch, block = 1024; n <= 64 * CB_MAXR.
-constexpr int CB_NB = 16, CB_KC = 64, CB_MAXR = 16;
 __global__ void __launch_bounds__(1024) chol_f64_blocked_kernel(const double* __restrict__ G, long g_batch_stride, int n,
                                                                 double* __restrict__ Lout, long l_batch_stride) {
     extern __shared__ __attribute__((aligned(16))) double sm64[];
@@ -1393,8 +1401,6 @@ __global__ void __launch_bounds__(128) student_grad_kernel(const T* __restrict__
 // (77 MB written + 77 MB read at cfg-2) and a launch whose 49-row GEMMs left two thirds of each MFMA tile empty.
 // RP <= n_t <= 4 RP; 16-byte aligned token rows; D % 4 == 0.
 // ---------------------------------------------------------------------------
-constexpr int SG_W = 64;          // slab width in features
-constexpr int SG_LD = SG_W + 4;   // row stride of the H slab in LDS
 template <typename T, int RP>
 __global__ void __launch_bounds__(256) student_grad_fused_kernel(
     const void* const* __restrict__ x_ptrs, long sb, long sn, int n_s, int n_t, int D, const float* __restrict__ omega,
@@ -1517,6 +1523,15 @@ __global__ void __launch_bounds__(128) resample_tokens_adjoint_kernel(const floa
 
 using namespace basd;
 
+// launch(T{}) for the element type behind a BASD_DTYPE_* code of token / attention tensors
+template <typename F>
+static int with_token_type(int dtype, F&& launch) {
+    if (dtype == BASD_DTYPE_F32) launch(float{});
+    else if (dtype == BASD_DTYPE_BF16) launch(__hip_bfloat16{});
+    else return BASD_EINVAL;
+    return BASD_OK;
+}
+
 extern "C" {
 
 // relational.py:22-34 on the layer-mixed attention.  attn_ptrs: device array of L pointers.
@@ -1529,46 +1544,25 @@ int basd_token_weights(const void* const* attn_ptrs, int dtype, const float* mix
     BASD_CHECK_ARG((n_a == n_s) == (atap0 == nullptr));
     BASD_CHECK_ARG((n_t == n_s) == (tap0 == nullptr));
     const size_t lds = sizeof(float) * (size_t)(n_a + n_s);
-    if (dtype == BASD_DTYPE_F32)
-        token_weights_kernel<float><<<B, 256, lds, stream>>>(attn_ptrs, mix, L, sb, sh, sq, sk, H, A, has_cls, n_a, n_t, n_s, atap0, atap1, alam, tap0, tap1, lam, omega, omega_t, raw_out);
-    else if (dtype == BASD_DTYPE_BF16)
-        token_weights_kernel<__hip_bfloat16><<<B, 256, lds, stream>>>(attn_ptrs, mix, L, sb, sh, sq, sk, H, A, has_cls, n_a, n_t, n_s, atap0, atap1, alam, tap0, tap1, lam, omega, omega_t, raw_out);
-    else
-        return BASD_EINVAL;
+    BASD_TRY(with_token_type(dtype, [&](auto t) {
+        token_weights_kernel<decltype(t)><<<B, 256, lds, stream>>>(attn_ptrs, mix, L, sb, sh, sq, sk, H, A, has_cls, n_a, n_t, n_s, atap0, atap1, alam, tap0, tap1, lam, omega, omega_t, raw_out);
+    }));
     BASD_RETURN_LAST();
 }
 
-// relational.py:36-45 (student half) + the transpose of combined.py:9-14.
+// relational.py:36-45 (student half) + the transpose of combined.py:9-14, for one layer: the general form, for any
+// row alignment and any number of student tokens (basd_student_project_multi: all layers, vectorised, where it applies).
 // tr_s: (B, ceil(D/64)) per-slab partial traces (summed by basd_procrustes_finalize).
 int basd_student_project(const void* x, int dtype, long sb, long sn, int B, int n_s, int n_t, int D,
                          const float* omega, const int* tap0, const int* tap1, const float* lam, const int* range0,
                          const int* range1, float* mu, float* tr_s, float* a_prime, hipStream_t stream) {
     BASD_CHECK_ARG(x && omega && mu && tr_s && a_prime && B > 0 && n_s > 0 && n_t > 0 && D > 0);
     BASD_CHECK_ARG((n_t == n_s) == (tap0 == nullptr));
-    const size_t lds = sizeof(float) * (size_t)n_s;
-    const dim3 grid((D + 63) / 64, B);
-    // LDS-staged variant: 16-byte aligned row quads and a slab that fits
-    const int esz = dtype == BASD_DTYPE_F32 ? 4 : 2;
-    const size_t lds_slab = sizeof(float) * (size_t)n_s * 65;
-    const bool staged = D % 4 == 0 && ((uintptr_t)x * 1) % 16 == 0 && (sb * esz) % 16 == 0 && (sn * esz) % 16 == 0 &&
-                        (esz == 4 || D % 8 == 0) && lds_slab <= 64 * 1024;      // >= 2 workgroups per CU
-    if (dtype == BASD_DTYPE_F32) {
-        if (staged) {
-            (void)hipFuncSetAttribute((const void*)student_project_lds_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_slab);
-            student_project_lds_kernel<float><<<grid, 256, lds_slab, stream>>>((const float*)x, sb, sn, n_s, n_t, D, omega, tap0, tap1, lam, range0, range1, mu, tr_s, a_prime);
-        } else {
-            student_project_kernel<float><<<grid, 256, lds, stream>>>((const float*)x, sb, sn, n_s, n_t, D, omega, tap0, tap1, lam, range0, range1, mu, tr_s, a_prime);
-        }
-    } else if (dtype == BASD_DTYPE_BF16) {
-        if (staged) {
-            (void)hipFuncSetAttribute((const void*)student_project_lds_kernel<__hip_bfloat16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_slab);
-            student_project_lds_kernel<__hip_bfloat16><<<grid, 256, lds_slab, stream>>>((const __hip_bfloat16*)x, sb, sn, n_s, n_t, D, omega, tap0, tap1, lam, range0, range1, mu, tr_s, a_prime);
-        } else {
-            student_project_kernel<__hip_bfloat16><<<grid, 256, lds, stream>>>((const __hip_bfloat16*)x, sb, sn, n_s, n_t, D, omega, tap0, tap1, lam, range0, range1, mu, tr_s, a_prime);
-        }
-    } else {
-        return BASD_EINVAL;
-    }
+    const dim3 grid(plan::trace_slabs(D, SP_W1), B);
+    BASD_TRY(with_token_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        student_project_kernel<T><<<grid, 256, plan::project_lds(n_s), stream>>>((const T*)x, sb, sn, n_s, n_t, D, omega, tap0, tap1, lam, range0, range1, mu, tr_s, a_prime);
+    }));
     BASD_RETURN_LAST();
 }
 
@@ -1579,18 +1573,13 @@ int basd_teacher_center(const void* const* tok_ptrs, int dtype, const float* mix
                         float* mu, float* tc, hipStream_t stream) {
     BASD_CHECK_ARG(tok_ptrs && mix && omega_t && mu && tc && L > 0 && B > 0 && n > 0 && D > 0);
     BASD_CHECK_ARG((g0 == nullptr) == (g1 == nullptr) && (g0 == nullptr) == (glam == nullptr));
-    const size_t lds = sizeof(float) * ((size_t)n * 65 + n + 64);
-    if (lds > 150 * 1024) return BASD_EUNSUPPORTED;
+    if (!plan::center_fits(n)) return BASD_EUNSUPPORTED;
     const dim3 grid((D + 63) / 64, B);
-    if (dtype == BASD_DTYPE_F32) {
-        (void)hipFuncSetAttribute((const void*)teacher_center_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        teacher_center_kernel<float><<<grid, 256, lds, stream>>>(tok_ptrs, mix, L, sb, sn, sd, n, D, g0, g1, glam, omega_t, mu, tc);
-    } else if (dtype == BASD_DTYPE_BF16) {
-        (void)hipFuncSetAttribute((const void*)teacher_center_kernel<__hip_bfloat16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        teacher_center_kernel<__hip_bfloat16><<<grid, 256, lds, stream>>>(tok_ptrs, mix, L, sb, sn, sd, n, D, g0, g1, glam, omega_t, mu, tc);
-    } else {
-        return BASD_EINVAL;
-    }
+    BASD_TRY(with_token_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        (void)hipFuncSetAttribute((const void*)teacher_center_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        teacher_center_kernel<T><<<grid, 256, plan::center_lds(n), stream>>>(tok_ptrs, mix, L, sb, sn, sd, n, D, g0, g1, glam, omega_t, mu, tc);
+    }));
     BASD_RETURN_LAST();
 }
 
@@ -1603,104 +1592,14 @@ int basd_teacher_center_multi(const void* const* tok_ptrs, int dtype, const floa
     BASD_CHECK_ARG(tok_ptrs && mix && omega_t && mu && tc && L > 0 && G > 0 && B > 0 && n > 0 && D > 0);
     BASD_CHECK_ARG((g0 == nullptr) == (g1 == nullptr) && (g0 == nullptr) == (glam == nullptr));
     BASD_CHECK_ARG(B <= 65535);
-    const size_t lds = sizeof(float) * ((size_t)G * n * (TCM_W + 1) + (size_t)G * n + (size_t)G * TCM_W);
-    if (G > TCM_G || lds > 150 * 1024) return BASD_EUNSUPPORTED;
+    if (!plan::center_multi_applies(G, n)) return BASD_EUNSUPPORTED;
     const dim3 grid((D + TCM_W - 1) / TCM_W, B);
-    if (dtype == BASD_DTYPE_F32) {
-        (void)hipFuncSetAttribute((const void*)teacher_center_multi_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        teacher_center_multi_kernel<float><<<grid, 256, lds, stream>>>(tok_ptrs, mix, L, G, sb, sn, sd, n, D, g0, g1, glam, omega_t, mu, tc);
-    } else if (dtype == BASD_DTYPE_BF16) {
-        (void)hipFuncSetAttribute((const void*)teacher_center_multi_kernel<__hip_bfloat16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        teacher_center_multi_kernel<__hip_bfloat16><<<grid, 256, lds, stream>>>(tok_ptrs, mix, L, G, sb, sn, sd, n, D, g0, g1, glam, omega_t, mu, tc);
-    } else {
-        return BASD_EINVAL;
-    }
+    BASD_TRY(with_token_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        (void)hipFuncSetAttribute((const void*)teacher_center_multi_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        teacher_center_multi_kernel<T><<<grid, 256, plan::center_multi_lds(G, n), stream>>>(tok_ptrs, mix, L, G, sb, sn, sd, n, D, g0, g1, glam, omega_t, mu, tc);
+    }));
     BASD_RETURN_LAST();
-}
-
-// The same for fp32 tokens on the teacher's own grid with 16-byte aligned rows (ViT teachers: cfg-4): a thread owns FOUR
-// consecutive features, the layers are read four at a time with all loads in flight before the first use (the scalar form
-// issues one 4-byte load per layer and waits for it: 2.5 TB/s over 24 layers of 103 MB).  Falls back to the scalar form
-// inside the launch when a layer's base pointer is not 16-byte aligned (wave-uniform).
-__global__ void __launch_bounds__(256) teacher_mix_stream_v4_kernel(
-    const void* const* __restrict__ tok_ptrs, const float* __restrict__ mix, int L, int G, long sb, long sn, int n, int D,
-    const float* __restrict__ omega_t, float* __restrict__ Tc, float* __restrict__ chunk_sum) {
-    const int chunk = blockIdx.x, b = blockIdx.y, B = gridDim.y, tid = threadIdx.x;
-    const int j_lo = chunk * TCS_ROWS, j_hi = j_lo + TCS_ROWS < n ? j_lo + TCS_ROWS : n;
-    bool aligned = true;
-    for (int l = 0; l < L; ++l) aligned = aligned && (((uintptr_t)tok_ptrs[l]) & 15) == 0;
-    if (!aligned) {       // uniform over the launch
-        for (int d = tid; d < D; d += 256) {
-            float musum[TCM_G] = {0.f, 0.f, 0.f, 0.f};
-            for (int j = j_lo; j < j_hi; ++j) {
-                const long o0 = b * sb + (long)j * sn + d;
-                float v[TCM_G] = {0.f, 0.f, 0.f, 0.f};
-                for (int l = 0; l < L; ++l) {
-                    const float x = ldg_f32((const BASD_GLOBAL_AS float*)tok_ptrs[l] + o0);
-#pragma unroll
-                    for (int g = 0; g < TCM_G; ++g)
-                        if (g < G) v[g] = fmaf(mix[g * L + l], x, v[g]);
-                }
-#pragma unroll
-                for (int g = 0; g < TCM_G; ++g)
-                    if (g < G) {
-                        Tc[(((long)g * B + b) * n + j) * D + d] = v[g];
-                        musum[g] = fmaf(omega_t[((long)g * B + b) * n + j], v[g], musum[g]);
-                    }
-            }
-#pragma unroll
-            for (int g = 0; g < TCM_G; ++g)
-                if (g < G) chunk_sum[(((long)chunk * G + g) * B + b) * D + d] = musum[g];
-        }
-        return;
-    }
-    for (int d = 4 * tid; d < D; d += 1024) {
-        float4 musum[TCM_G];
-#pragma unroll
-        for (int g = 0; g < TCM_G; ++g) musum[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int j = j_lo; j < j_hi; ++j) {
-            const long o0 = b * sb + (long)j * sn + d;
-            float4 v[TCM_G];
-#pragma unroll
-            for (int g = 0; g < TCM_G; ++g) v[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-            int l = 0;
-            for (; l + 4 <= L; l += 4) {
-                float4 x[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) x[q] = ld4f((const BASD_GLOBAL_AS float*)tok_ptrs[l + q] + o0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int g = 0; g < TCM_G; ++g)
-                        if (g < G) {
-                            const float m = mix[g * L + l + q];
-                            v[g].x = fmaf(m, x[q].x, v[g].x); v[g].y = fmaf(m, x[q].y, v[g].y);
-                            v[g].z = fmaf(m, x[q].z, v[g].z); v[g].w = fmaf(m, x[q].w, v[g].w);
-                        }
-            }
-            for (; l < L; ++l) {
-                const float4 x = ld4f((const BASD_GLOBAL_AS float*)tok_ptrs[l] + o0);
-#pragma unroll
-                for (int g = 0; g < TCM_G; ++g)
-                    if (g < G) {
-                        const float m = mix[g * L + l];
-                        v[g].x = fmaf(m, x.x, v[g].x); v[g].y = fmaf(m, x.y, v[g].y);
-                        v[g].z = fmaf(m, x.z, v[g].z); v[g].w = fmaf(m, x.w, v[g].w);
-                    }
-            }
-#pragma unroll
-            for (int g = 0; g < TCM_G; ++g)
-                if (g < G) {
-                    *(float4*)(Tc + (((long)g * B + b) * n + j) * D + d) = v[g];
-                    const float om = omega_t[((long)g * B + b) * n + j];
-                    musum[g].x = fmaf(om, v[g].x, musum[g].x); musum[g].y = fmaf(om, v[g].y, musum[g].y);
-                    musum[g].z = fmaf(om, v[g].z, musum[g].z); musum[g].w = fmaf(om, v[g].w, musum[g].w);
-                }
-        }
-#pragma unroll
-        for (int g = 0; g < TCM_G; ++g)
-            if (g < G) *(float4*)(chunk_sum + (((long)chunk * G + g) * B + b) * D + d) = musum[g];
-    }
 }
 
 // Streaming form of basd_teacher_center_multi for row-major teacher tokens (see teacher_mix_stream_kernel): scratch of
@@ -1708,24 +1607,21 @@ __global__ void __launch_bounds__(256) teacher_mix_stream_v4_kernel(
 // contiguous.
 long basd_teacher_center_stream_scratch_floats(int G, int B, int n, int D) {
     if (G <= 0 || B <= 0 || n <= 0 || D <= 0) return 0;
-    return (long)((n + TCS_ROWS - 1) / TCS_ROWS) * G * B * D;
+    return plan::stream_scratch_floats(G, B, n, D);
 }
 int basd_teacher_center_stream(const void* const* tok_ptrs, int dtype, const float* mix, int L, int G, long sb, long sn,
                                long sd, int B, int n, int D, const int* g0, const int* g1, const float* glam,
                                const float* omega_t, float* mu, float* tc, float* scratch, hipStream_t stream) {
     BASD_CHECK_ARG(tok_ptrs && mix && omega_t && mu && tc && scratch && L > 0 && G > 0 && B > 0 && n > 0 && D > 0);
     BASD_CHECK_ARG((g0 == nullptr) == (g1 == nullptr) && (g0 == nullptr) == (glam == nullptr));
-    if (G > TCM_G || sd != 1 || B > 65535 || (long)G * B > 65535) return BASD_EUNSUPPORTED;
-    const int chunks = (n + TCS_ROWS - 1) / TCS_ROWS;
-    if (dtype == BASD_DTYPE_F32 && g0 == nullptr && D % 4 == 0 && sb % 4 == 0 && sn % 4 == 0 && (((uintptr_t)tc) & 15) == 0 &&
-        (((uintptr_t)scratch) & 15) == 0)
+    if (!plan::stream_applies(G, sd, B)) return BASD_EUNSUPPORTED;
+    const int chunks = plan::stream_chunks(n);
+    if (plan::stream_v4_applies(dtype, g0 != nullptr, sb, sn, D, tc, scratch))
         teacher_mix_stream_v4_kernel<<<dim3(chunks, B), 256, 0, stream>>>(tok_ptrs, mix, L, G, sb, sn, n, D, omega_t, tc, scratch);
-    else if (dtype == BASD_DTYPE_F32)
-        teacher_mix_stream_kernel<float><<<dim3(chunks, B), 256, 0, stream>>>(tok_ptrs, mix, L, G, sb, sn, sd, n, D, g0, g1, glam, omega_t, tc, scratch);
-    else if (dtype == BASD_DTYPE_BF16)
-        teacher_mix_stream_kernel<__hip_bfloat16><<<dim3(chunks, B), 256, 0, stream>>>(tok_ptrs, mix, L, G, sb, sn, sd, n, D, g0, g1, glam, omega_t, tc, scratch);
     else
-        return BASD_EINVAL;
+        BASD_TRY(with_token_type(dtype, [&](auto t) {
+            teacher_mix_stream_kernel<decltype(t)><<<dim3(chunks, B), 256, 0, stream>>>(tok_ptrs, mix, L, G, sb, sn, sd, n, D, g0, g1, glam, omega_t, tc, scratch);
+        }));
     teacher_center_apply_kernel<<<dim3((D + 255) / 256, chunks, G * B), 256, 0, stream>>>(scratch, chunks, n, D, mu, tc);
     BASD_RETURN_LAST();
 }
@@ -1761,18 +1657,16 @@ int basd_gram_f64_split(const float* p, long p_batch_stride, int n, int D, int b
 int basd_chol_f64(const double* g, long g_batch_stride, int n, int batch, double* l, long l_batch_stride,
                   hipStream_t stream) {
     BASD_CHECK_ARG(g && l && n > 0 && batch > 0);
-    const size_t lds = sizeof(double) * ((size_t)n * (n + 1) / 2 + n);
-    if (lds > 158 * 1024) {
+    if (!plan::chol_in_lds(n)) {
         // past LDS: panels of the factor in LDS, the factor itself in global memory
-        if (n > 64 * CB_MAXR) return BASD_EUNSUPPORTED;
-        const size_t lds_b = sizeof(double) * ((size_t)n * CB_NB + (size_t)CB_NB * (CB_KC + 1));
+        if (!plan::chol_blocked_fits(n)) return BASD_EUNSUPPORTED;
         (void)hipFuncSetAttribute((const void*)chol_f64_blocked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        chol_f64_blocked_kernel<<<batch, 1024, lds_b, stream>>>(g, g_batch_stride, n, l, l_batch_stride);
+        chol_f64_blocked_kernel<<<batch, 1024, plan::chol_blocked_lds(n), stream>>>(g, g_batch_stride, n, l, l_batch_stride);
         BASD_RETURN_LAST();
     }
     (void)hipFuncSetAttribute((const void*)chol_f64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
     const int threads = n >= 128 ? 1024 : n >= 64 ? 512 : 256;
-    chol_f64_kernel<<<batch, threads, lds, stream>>>(g, g_batch_stride, n, l, l_batch_stride);
+    chol_f64_kernel<<<batch, threads, plan::chol_lds(n), stream>>>(g, g_batch_stride, n, l, l_batch_stride);
     BASD_RETURN_LAST();
 }
 
@@ -1848,10 +1742,10 @@ int basd_procrustes_finalize(const float* w, long w_batch_stride, const float* s
                              float* tr_t, float* nuc, float* loss, float* k_prime, hipStream_t stream) {
     BASD_CHECK_ARG(w && sigma && gb && omega && tr_s_part && tr_s && tr_t && nuc && loss && n > 0 && batch > 0 && tr_slabs > 0);
     BASD_CHECK_ARG(t_period > 0);
-    size_t lds = sizeof(float) * ((size_t)n + (k_prime ? (size_t)n * n : 0));
-    const bool tiled = lds > 156 * 1024;       // K' past LDS: the per-sample terms here, K' by a tiled kernel
-    if (tiled) lds = sizeof(float) * (size_t)n;
-    if (lds > 156 * 1024) return BASD_EUNSUPPORTED;
+    size_t lds = plan::finalize_lds(n, k_prime != nullptr);
+    const bool tiled = !plan::finalize_fits(lds);       // K' past LDS: the per-sample terms here, K' by a tiled kernel
+    if (tiled) lds = plan::finalize_lds(n, false);
+    if (!plan::finalize_fits(lds)) return BASD_EUNSUPPORTED;
     (void)hipFuncSetAttribute((const void*)procrustes_finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     procrustes_finalize_kernel<<<batch, 256, lds, stream>>>(w, w_batch_stride, sigma, n, n_s, gb, g_batch_stride, omega, tap0, tap1, lam, tr_s_part, tr_slabs, tr_s, tr_t, nuc, loss, tiled ? nullptr : k_prime, t_period);
     if (tiled) {
@@ -1873,10 +1767,8 @@ int basd_procrustes_finish_transposed(const float* w, long w_batch_stride, const
                                       float* k_prime, hipStream_t stream) {
     BASD_CHECK_ARG(w && sigma && gb && omega && tr_s_part && tr_s && tr_t && nuc && loss && lb && k_prime && n > 0 &&
                    batch > 0 && tr_slabs > 0 && t_period > 0 && lb_period > 0);
-    if (n > 64 || batch > 65535) return BASD_EUNSUPPORTED;
-    const int nq = (n + 3) / 4, np = 4 * nq, ld = (nq & 1) ? np : np + 4;
-    const size_t lds = sizeof(float) * (size_t)(3 * np * ld + np);      // <= 52480 bytes
-    procrustes_finish_t_kernel<<<batch, 256, lds, stream>>>(w, w_batch_stride, sigma, n, n_s, gb, g_batch_stride, omega, tap0, tap1, lam, tr_s_part, tr_slabs, tr_s, tr_t, nuc, loss, t_period, lb, l_batch_stride, lb_period, k_prime);
+    if (!plan::finish_transposed_applies(n, batch)) return BASD_EUNSUPPORTED;
+    procrustes_finish_t_kernel<<<batch, 256, plan::finish_transposed_lds(n), stream>>>(w, w_batch_stride, sigma, n, n_s, gb, g_batch_stride, omega, tap0, tap1, lam, tr_s_part, tr_slabs, tr_s, tr_t, nuc, loss, t_period, lb, l_batch_stride, lb_period, k_prime);
     BASD_RETURN_LAST();
 }
 
@@ -1892,12 +1784,9 @@ int basd_student_grad_multi(const void* const* x_ptrs, int dtype, long sb, long 
     BASD_CHECK_ARG((gomega == nullptr) || (tnorm2 != nullptr));
     BASD_CHECK_ARG(E <= 65535 && B <= 65535);
     const dim3 grid(n_s, B, E);
-    if (dtype == BASD_DTYPE_F32)
-        student_grad_kernel<float><<<grid, 128, 0, stream>>>(nullptr, x_ptrs, sb, sn, n_s, n_t, D, omega, omega_e_stride, mu, h, tap0, tap1, lam, scale_ptr, scale_const, dx, tnorm2, gomega);
-    else if (dtype == BASD_DTYPE_BF16)
-        student_grad_kernel<__hip_bfloat16><<<grid, 128, 0, stream>>>(nullptr, x_ptrs, sb, sn, n_s, n_t, D, omega, omega_e_stride, mu, h, tap0, tap1, lam, scale_ptr, scale_const, dx, tnorm2, gomega);
-    else
-        return BASD_EINVAL;
+    BASD_TRY(with_token_type(dtype, [&](auto t) {
+        student_grad_kernel<decltype(t)><<<grid, 128, 0, stream>>>(nullptr, x_ptrs, sb, sn, n_s, n_t, D, omega, omega_e_stride, mu, h, tap0, tap1, lam, scale_ptr, scale_const, dx, tnorm2, gomega);
+    }));
     BASD_RETURN_LAST();
 }
 
@@ -1912,30 +1801,21 @@ int basd_student_grad_fused(const void* const* x_ptrs, int dtype, long sb, long 
     BASD_CHECK_ARG(x_ptrs && omega && mu && k_prime && a_prime && scale_ptr && dx && E > 0 && B > 0 && n_s > 0 && n_t > 0 && D > 0);
     BASD_CHECK_ARG((n_t == n_s) == (tap0 == nullptr));
     BASD_CHECK_ARG(E <= 65535 && B <= 65535);
-    const int esz = dtype == BASD_DTYPE_F32 ? 4 : 2;
-    const bool ok = ptrs_16B_aligned && n_t <= 64 && D % 4 == 0 && (sb * esz) % 16 == 0 && (sn * esz) % 16 == 0 &&
-                    (esz == 4 || D % 8 == 0) && ((uintptr_t)a_prime & 15) == 0 && ((uintptr_t)mu & 15) == 0 &&
-                    ((uintptr_t)dx & 15) == 0;
-    if (!ok) return BASD_EUNSUPPORTED;
-    if (n_t < 4) return BASD_EUNSUPPORTED;
+    if (!plan::grad_fused_applies(ptrs_16B_aligned, dtype, sb, sn, D, n_t, a_prime, mu, dx)) return BASD_EUNSUPPORTED;
     const int rp = (n_t + 3) / 4;
-    const size_t lds = sizeof(float) * (size_t)n_t * (SG_W + SG_LD);
+    const size_t lds = plan::grad_fused_lds(n_t);
     const dim3 grid((D + SG_W - 1) / SG_W, B, E);
-#define LAUNCH_SGF(TY, RP)                                                                                           \
-    student_grad_fused_kernel<TY, RP><<<grid, 256, lds, stream>>>(x_ptrs, sb, sn, n_s, n_t, D, omega, omega_e_stride, mu, \
-                                                                  k_prime, a_prime, tap0, tap1, lam, scale_ptr,      \
-                                                                  scale_const, dx)
-#define LAUNCH_SGF_T(TY)                 \
-    do {                                 \
-        if (rp <= 4) LAUNCH_SGF(TY, 4);  \
-        else if (rp <= 8) LAUNCH_SGF(TY, 8);  \
-        else if (rp <= 13) LAUNCH_SGF(TY, 13); \
-        else LAUNCH_SGF(TY, 16);         \
-    } while (0)
-    if (dtype == BASD_DTYPE_F32) LAUNCH_SGF_T(float);
-    else if (dtype == BASD_DTYPE_BF16) LAUNCH_SGF_T(__hip_bfloat16);
-    else return BASD_EINVAL;
-#undef LAUNCH_SGF_T
+#define LAUNCH_SGF(RP)                                                                                              \
+    student_grad_fused_kernel<T, RP><<<grid, 256, lds, stream>>>(x_ptrs, sb, sn, n_s, n_t, D, omega, omega_e_stride, mu, \
+                                                                 k_prime, a_prime, tap0, tap1, lam, scale_ptr,      \
+                                                                 scale_const, dx)
+    BASD_TRY(with_token_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (rp <= 4) LAUNCH_SGF(4);
+        else if (rp <= 8) LAUNCH_SGF(8);
+        else if (rp <= 13) LAUNCH_SGF(13);
+        else LAUNCH_SGF(16);
+    }));
 #undef LAUNCH_SGF
     BASD_RETURN_LAST();
 }
@@ -1950,21 +1830,14 @@ int basd_student_project_multi(const void* const* x_ptrs, int dtype, long sb, lo
     BASD_CHECK_ARG(x_ptrs && omega && mu && tr_s && a_prime && E > 0 && B > 0 && n_s > 0 && n_t > 0 && D > 0);
     BASD_CHECK_ARG((n_t == n_s) == (tap0 == nullptr));
     BASD_CHECK_ARG(E <= 65535 && B <= 65535);
-    const int esz = dtype == BASD_DTYPE_F32 ? 4 : 2;
-    const size_t lds = sizeof(float) * ((size_t)n_s * SP_W + 5 * (size_t)n_s);
-    const bool ok = ptrs_16B_aligned && D % 4 == 0 && (sb * esz) % 16 == 0 && (sn * esz) % 16 == 0 &&
-                    (esz == 4 || D % 8 == 0) && lds <= 96 * 1024;
-    if (!ok) return BASD_EUNSUPPORTED;
-    const dim3 grid((D + SP_W - 1) / SP_W, B, E);
-    if (dtype == BASD_DTYPE_F32) {
-        (void)hipFuncSetAttribute((const void*)student_project_v4_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        student_project_v4_kernel<float><<<grid, 256, lds, stream>>>(x_ptrs, sb, sn, n_s, n_t, D, omega, omega_e_stride, tap0, tap1, lam, range0, range1, mu, tr_s, a_prime);
-    } else if (dtype == BASD_DTYPE_BF16) {
-        (void)hipFuncSetAttribute((const void*)student_project_v4_kernel<__hip_bfloat16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        student_project_v4_kernel<__hip_bfloat16><<<grid, 256, lds, stream>>>(x_ptrs, sb, sn, n_s, n_t, D, omega, omega_e_stride, tap0, tap1, lam, range0, range1, mu, tr_s, a_prime);
-    } else {
-        return BASD_EINVAL;
-    }
+    if (!plan::project_multi_applies(ptrs_16B_aligned, dtype, sb, sn, D, n_s)) return BASD_EUNSUPPORTED;
+    const size_t lds = plan::project_multi_lds(n_s);
+    const dim3 grid(plan::trace_slabs(D, SP_W), B, E);
+    BASD_TRY(with_token_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        (void)hipFuncSetAttribute((const void*)student_project_v4_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        student_project_v4_kernel<T><<<grid, 256, lds, stream>>>(x_ptrs, sb, sn, n_s, n_t, D, omega, omega_e_stride, tap0, tap1, lam, range0, range1, mu, tr_s, a_prime);
+    }));
     BASD_RETURN_LAST();
 }
 
@@ -1973,12 +1846,10 @@ int basd_resample_tokens(const void* x, int dtype, long sb, long sn, long sd, in
                          const int* tap0, const int* tap1, const float* lam, float* out, hipStream_t stream) {
     BASD_CHECK_ARG(x && tap0 && tap1 && lam && out && B > 0 && n_in > 0 && n_out > 0 && D > 0);
     const dim3 grid(n_out, B);
-    if (dtype == BASD_DTYPE_F32)
-        resample_tokens_kernel<float><<<grid, 128, 0, stream>>>((const float*)x, sb, sn, sd, n_in, n_out, D, tap0, tap1, lam, out);
-    else if (dtype == BASD_DTYPE_BF16)
-        resample_tokens_kernel<__hip_bfloat16><<<grid, 128, 0, stream>>>((const __hip_bfloat16*)x, sb, sn, sd, n_in, n_out, D, tap0, tap1, lam, out);
-    else
-        return BASD_EINVAL;
+    BASD_TRY(with_token_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        resample_tokens_kernel<T><<<grid, 128, 0, stream>>>((const T*)x, sb, sn, sd, n_in, n_out, D, tap0, tap1, lam, out);
+    }));
     BASD_RETURN_LAST();
 }
 
