@@ -1147,6 +1147,117 @@ int basd_jpeg_decode_parallel(const unsigned char* src, long src_bytes, unsigned
                               const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status,
                               long max_blocks, long max_pixels, int sub_bytes, hipStream_t stream);
 
+/* ---- Pillow-exact 8-bit PNG decoding of a batch of files in two launches ------------------------------------ */
+
+#define BASD_PNG_MAX_SIDE 16384
+#define BASD_PNG_MAX_BATCH 65535
+
+#define BASD_PNG_KIND_STREAM 0       /* the IDAT payloads of a PNG file, inflated and unfiltered on the device */
+#define BASD_PNG_KIND_RAW 1          /* width * height * 3 RGB bytes made by the host fallback, copied into place */
+
+/* The per-image status word (0: decoded); the batch's status word is the OR of 1 << (code - 1). */
+#define BASD_PNG_BAD_RECORD 1        /* a field of the record outside its bounds (nothing of the image is read) */
+#define BASD_PNG_BAD_BLOCK 2         /* deflate block type 3 */
+#define BASD_PNG_BAD_STORED 3        /* a stored block whose LEN is not ~NLEN */
+#define BASD_PNG_BAD_LENGTHS 4       /* code lengths that are no prefix code (see below) */
+#define BASD_PNG_BAD_CODE 5          /* a bit pattern or a symbol that is no code (see below) */
+#define BASD_PNG_BAD_DISTANCE 6      /* a match that reaches back past the first byte produced */
+#define BASD_PNG_TRUNCATED 7         /* the input ends before the final block, or before the 4 bytes behind it, do */
+#define BASD_PNG_WRONG_LENGTH 8      /* the stream produces more or fewer bytes than the scanlines need */
+#define BASD_PNG_BAD_FILTER 9        /* a scanline whose filter type is above 4 */
+#define BASD_PNG_BAD_ADLER 10        /* the Adler-32 of the inflated bytes is not the one behind the final block */
+
+/* One row of the device table, one per image (64 bytes). */
+typedef struct BasdPngRecord {
+    long long src_offset;         /* byte buffer: the concatenated IDAT payloads, zlib header first (or the raw pixels) */
+    long long out_offset;         /* byte offset of the image (HWC RGB, width * height * 3 bytes) in the output */
+    long long ws_offset;          /* workspace: the filtered scanlines, height * (width * bpp + 1) bytes (a multiple of 16) */
+    long long plte_offset;        /* byte buffer: 768 bytes, PLTE padded with zeros (read for colour type 3 only) */
+    int src_len;                  /* bytes at src_offset (< 2^31 - 16); of a raw record width * height * 3 */
+    int kind;                     /* BASD_PNG_KIND_* */
+    int width, height;
+    int color_type;               /* 0, 2, 3, 4 or 6 */
+    int pad[3];
+} BasdPngRecord;
+
+/* Bytes at the start of the workspace that the launches keep per batch: B int32 status words, then B int32 with the
+ * offset (from src_offset) of the 4 Adler-32 bytes, i.e. of the first byte boundary behind the final block. */
+long basd_png_status_bytes(int B);
+
+/* replaces: the same `Image.open(...).convert("RGB")` of the reference loader's workers for the datasets that ship PNG
+ *           files (configs/experiment/basd_cifar100.yaml: uoft-cs/cifar100).
+ * The arguments are those of basd_jpeg_decode, with max_filtered the largest height * (width * bpp + 1) of a stream
+ * record.  This text is the specification; basd_amd.png.inflate_reference / decode_reference restate it in Python, the
+ * kernels equal them byte for byte and status for status, and they equal Pillow 12
+ * `np.asarray(Image.open(f).convert("RGB"))` on the files in scope.
+ *
+ * Scope (the host's basd_amd.png.parse_png decides; everything else is a raw record made by the fallback): bit depth 8,
+ * colour type 0 (gray), 2 (RGB), 3 (palette, PLTE present), 4 (gray + alpha) or 6 (RGBA), no interlace, compression and
+ * filter method 0, sides 1 .. BASD_PNG_MAX_SIDE, a zlib header that says deflate, a window of at most 32 KiB, no preset
+ * dictionary and passes its check (CMF * 256 + FLG divisible by 31).  Chunk CRCs are not checked (Pillow decodes a file
+ * whose IDAT CRC is wrong); tRNS, gAMA, iCCP, bKGD, acTL and every other ancillary chunk are ignored.
+ *
+ * Output: bpp = 1, 3, 1, 2, 4 bytes per pixel for colour types 0, 2, 3, 4, 6.  Gray is written three times, alpha is
+ * dropped (not composited), index i is bytes 3 i .. 3 i + 2 of the 768 palette bytes (entries past PLTE are 0, 0, 0).
+ *
+ * Inflate (RFC 1951) of src[2 .. src_len) -- the two header bytes are the host's -- into exactly
+ * n = height * (width * bpp + 1) bytes.  Bits are taken from the least significant end of each byte; past the end of
+ * the input the bits are zeros, and taking one of them is BASD_PNG_TRUNCATED, which is checked after every group of
+ * bits taken and before what they say is looked at.  Per block: 1 bit final, 2 bits type.
+ *   type 3: BASD_PNG_BAD_BLOCK.
+ *   type 0: the rest of the byte is dropped; LEN, NLEN (16 bits each); LEN != ~NLEN: BASD_PNG_BAD_STORED; more than
+ *           n bytes produced: BASD_PNG_WRONG_LENGTH; fewer than LEN bytes left: BASD_PNG_TRUNCATED; LEN bytes copied.
+ *   type 1: literal/length lengths 8 (0..143), 9 (144..255), 7 (256..279), 8 (280..287); 32 distance lengths of 5.
+ *   type 2: HLIT (5), HDIST (5), HCLEN (4); HLIT + 257 > 286 or HDIST + 1 > 30: BASD_PNG_BAD_LENGTHS; HCLEN + 4
+ *           lengths of 3 bits in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15; then HLIT + 257 + HDIST + 1
+ *           lengths by that code: 0..15 a length; 16: the previous length 3 + (2 bits) times (none before it:
+ *           BASD_PNG_BAD_LENGTHS); 17: zero 3 + (3 bits) times; 18: zero 11 + (7 bits) times; a repeat that runs
+ *           past the count, or no length for symbol 256: BASD_PNG_BAD_LENGTHS.
+ * A set of lengths is a code when it is not over-subscribed (sum of 2^-len <= 1) and complete (= 1); as in zlib, the
+ * literal/length and the distance set may also be incomplete when their longest code has 1 bit or they have no code at
+ * all; the code-length set may not.  Anything else is BASD_PNG_BAD_LENGTHS.  Codes are canonical (per length in
+ * symbol order, counting up, shorter lengths first), and are sent most significant bit first.  A symbol is found from
+ * the next 15 bits; where they begin with no code, 15 bits are taken and the result is BASD_PNG_BAD_CODE.  Symbols of
+ * a block, one at a time: < 256 a literal; 256 ends the block; 286, 287: BASD_PNG_BAD_CODE; else with i = symbol - 257:
+ * length 3 + i (i < 8), 258 (i = 28), else e = i / 4 - 1 extra bits and length 3 + ((4 + i % 4) << e) + extra; then a
+ * distance symbol d (30, 31: BASD_PNG_BAD_CODE): distance 1 + d (d < 4), else e = d / 2 - 1 extra bits and distance
+ * 1 + ((2 + d % 2) << e) + extra.  A distance larger than the count of bytes produced: BASD_PNG_BAD_DISTANCE.  A
+ * literal or a match that would produce byte n + 1: BASD_PNG_WRONG_LENGTH (checked after the distance).  Byte
+ * pos + j of a match is byte pos - distance + j % distance.  After the final block: fewer than n bytes:
+ * BASD_PNG_WRONG_LENGTH; the rest of the byte is dropped; fewer than 4 bytes left: BASD_PNG_TRUNCATED.  What follows
+ * those 4 bytes is ignored.
+ *
+ * Adler-32 of the n bytes b_0 .. b_(n-1): A = (1 + sum b_i) mod 65521, B = (n + sum (n - i) b_i) mod 65521; the 4
+ * bytes behind the final block, big-endian, must equal B * 65536 + A (else BASD_PNG_BAD_ADLER); then every scanline's
+ * first byte must be at most 4 (else BASD_PNG_BAD_FILTER).
+ *
+ * Unfilter (PNG 1.2, section 6): per scanline the filter byte, then width * bpp bytes x; with a the reconstructed
+ * byte bpp to the left, b the one above, c the one above a (0 outside the image), modulo 256: 0: x; 1: x + a; 2: x + b;
+ * 3: x + floor((a + b) / 2); 4: x + Paeth, where p = a + b - c, pa = |p - a|, pb = |p - b|, pc = |p - c| and the
+ * predictor is a if pa <= pb and pa <= pc, else b if pb <= pc, else c.
+ *
+ * Bad streams.  Every field of a record is checked against the byte buffer, the output and the workspace before it is
+ * used, every read of a stream against src_len, every write lands in the image's own ranges.  An image that fails has
+ * an all-zero output (nothing is written where its output range itself is out of bounds), its code in its status word
+ * and the code's bit in `status`; the other images are unaffected.  Every loop of the inflate takes at least one bit or
+ * produces at least one byte, and leaves at the first error, so a stream ends within 8 * src_len + n steps.
+ *
+ * Launches (TWO per batch, whatever B; no allocation, no memset, no wait for the device):
+ *   inflate    one workgroup of one wave per image.  The decode state is the same in all 64 lanes.  The three Huffman
+ *              tables live in LDS: lane 0 counts the lengths and assigns the codes, all lanes fill the 9-bit look-up
+ *              (longer codes are found by counting through the lengths).  A match is copied by the lanes together
+ *              out of a 32 KiB window of the output kept in LDS; every byte goes to the window and to the workspace.
+ *   unfilter   one workgroup of one wave per image: the Adler-32 and the filter bytes (lanes stride over the bytes,
+ *              64-bit sums), then bands of 64 scanlines as a skewed wavefront: lane l owns row r0 + l and
+ *              reconstructs pixel t - l at step t, the pixel above comes from lane l - 1 by a lane shift, the last
+ *              row of a band is written back for the next one; each pixel is written as RGB in the same step.  A
+ *              raw record's pixels are copied, a failed image's are zero.
+ * B == 0 launches nothing; the argument checks and BASD_EINVAL rules are those of basd_jpeg_decode (max_filtered and
+ * max_pixels at most what BASD_PNG_MAX_SIDE allows, a workspace of at least basd_png_status_bytes(B)). */
+int basd_png_decode(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
+                    const BasdPngRecord* records, unsigned char* ws, long ws_bytes, int* status, long max_filtered,
+                    long max_pixels, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ Sub-modules:
                of ragged batches of decoded uint8 images, both views in one launch
   ``jpeg``     ``JpegDecoder`` / ``pack_jpegs`` / ``collate_jpeg`` / ``parse_jpeg``: Pillow-exact baseline JPEG decoding of a
                batch of files' bytes into a ragged batch, three launches per batch
+  ``png``      ``PngDecoder`` / ``pack_pngs`` / ``collate_png`` / ``parse_png``: Pillow-exact 8-bit PNG decoding of a batch of
+               files' bytes into a ragged batch, two launches per batch
   ``prefetch``  ``DevicePrefetcher``: the input work of the next batch on a side stream while the step runs
   ``_launch``  what those one-launch stages share on the host: argument checks, dtype codes, the record-table uploader
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
@@ -31,8 +33,10 @@ from .resize import (CropParams, RaggedBatch, ResizeCrop, collate_ragged, draw_c
                      eval_window, pack_images)
 from .jpeg import (JpegBatch, JpegDecoder, UnsupportedJpeg, collate_jpeg, decode_reference,  # noqa: E402
                    pack_jpegs, parse_jpeg)
+from .png import PngBatch, PngDecoder, UnsupportedPng, collate_png, pack_pngs, parse_png  # noqa: E402
 from .prefetch import DevicePrefetcher  # noqa: E402
 
 __all__ = ["attn_importance", "AugmentParams", "TrivialAugment", "draw_augment_params", "CropParams", "RaggedBatch",
            "ResizeCrop", "collate_ragged", "draw_crop_params", "eval_window", "pack_images", "JpegBatch", "JpegDecoder",
-           "UnsupportedJpeg", "collate_jpeg", "decode_reference", "pack_jpegs", "parse_jpeg", "DevicePrefetcher"]
+           "UnsupportedJpeg", "collate_jpeg", "decode_reference", "pack_jpegs", "parse_jpeg", "PngBatch",
+           "PngDecoder", "UnsupportedPng", "collate_png", "pack_pngs", "parse_png", "DevicePrefetcher"]

@@ -131,6 +131,8 @@ SIGNATURES = {
     "basd_jpeg_status_bytes": [i32],
     "basd_jpeg_decode": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp],
     "basd_jpeg_decode_parallel": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, i32, vp],
+    "basd_png_status_bytes": [i32],
+    "basd_png_decode": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp],
 }
 
 class ProcrustesArgs(C.Structure):
@@ -179,7 +181,7 @@ EINVAL, EUNSUPPORTED = -1, -2        # BASD_EINVAL / BASD_EUNSUPPORTED of includ
 # sizing helpers declared `long` in include/basd_hip.h
 LONG_RESULTS = {"basd_tridiag_workspace_bytes", "basd_jacobi_twopass_workspace_bytes",
                 "basd_mix_grad_tokens_scratch_floats", "basd_teacher_center_stream_scratch_floats",
-                "basd_rank_certificate_scratch_bytes", "basd_sfadamw_launches", "basd_jpeg_status_bytes"}
+                "basd_rank_certificate_scratch_bytes", "basd_sfadamw_launches", "basd_jpeg_status_bytes", "basd_png_status_bytes"}
 
 _lock = threading.Lock()
 _lib = None

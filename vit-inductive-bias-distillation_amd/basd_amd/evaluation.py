@@ -111,7 +111,7 @@ def _label_smoothing_of(criterion) -> float:
 @torch.no_grad()
 def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_classes: int, valid_indices=None,
                    distributed: bool = False, image_stats=None, input_dtype=None, resize_crop=None,
-                   jpeg_decode=None, prefetch: int = 0, prefetch_stream=None) -> dict:
+                   jpeg_decode=None, png_decode=None, prefetch: int = 0, prefetch_stream=None) -> dict:
     """The reference's ``evaluate_model``: batches are dicts with ``pixel_values`` and ``label``; returns ``val_acc``,
     ``val_acc_top5`` (percent) and ``loss`` (mean of ``criterion`` over the samples); fewer than 5 evaluated classes
     raise ``ValueError``.  ``distributed=True``: every rank iterates its own shard and the counts are summed over the
@@ -126,11 +126,12 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
     CenterCrop``), which then takes the uint8 path above, so ``image_stats`` is needed (``ValueError`` otherwise).
     ``jpeg_decode``: a ``basd_amd.jpeg.JpegDecoder`` (it needs ``resize_crop``); with it ``images`` may be a ``JpegBatch``
     of the files' bytes (``collate_fn=collate_jpeg``), decoded on the device ahead of the resize launch.
+    ``png_decode``: a ``basd_amd.png.PngDecoder``, the same for a ``PngBatch`` (``collate_fn=collate_png``).
     ``prefetch``: an int >= 0 (``ValueError`` otherwise); the input half of up to that many batches (transfer, decode,
     resize, conversion, labels) runs ahead on a side stream (``basd_amd.prefetch.DevicePrefetcher``) while the model
     and the metrics launch of the batch before stay on the caller's; 0, the default, is the serial loop.
-    ``prefetch_stream``: a ``DevicePrefetcher``'s ``.stream`` to use for it instead of a new one.  ``resize_crop`` and
-    ``jpeg_decode`` belong to this call until it returns."""
+    ``prefetch_stream``: a ``DevicePrefetcher``'s ``.stream`` to use for it instead of a new one.  ``resize_crop``,
+    ``jpeg_decode`` and ``png_decode`` belong to this call until it returns."""
     label_smoothing = _label_smoothing_of(criterion)
     if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
         raise ValueError(f"prefetch must be an int >= 0 (got {prefetch!r})")
@@ -139,6 +140,9 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
                          "the device; got image_stats=None")
     if jpeg_decode is not None and resize_crop is None:
         raise ValueError("jpeg_decode needs resize_crop=ResizeCrop(...): the decoded images are a ragged batch; got "
+                         "resize_crop=None")
+    if png_decode is not None and resize_crop is None:
+        raise ValueError("png_decode needs resize_crop=ResizeCrop(...): the decoded images are a ragged batch; got "
                          "resize_crop=None")
     model.eval()
     device = next(model.parameters()).device
@@ -160,6 +164,10 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
                 from .jpeg import JpegBatch
                 if isinstance(images, JpegBatch):
                     images = jpeg_decode(images)
+            if png_decode is not None:
+                from .png import PngBatch
+                if isinstance(images, PngBatch):
+                    images = png_decode(images)
             inputs = resize_crop(images, views=("clean",))["clean"]
         else:
             inputs = batch["pixel_values"]

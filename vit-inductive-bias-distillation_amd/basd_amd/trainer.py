@@ -108,6 +108,8 @@ class Trainer:
     into the ``RaggedBatch`` the resize launch takes; a ``RaggedBatch`` is taken as before.  ``"parallel"`` is ``True`` with
     ``JpegDecoder(entropy="parallel")``: the entropy stage decodes inside a segment with a workgroup's lanes instead of
     one lane per segment (the same bytes; what it gains is in DESIGN.md section 8).  ``False``: no decoder.
+    ``png_decode``: ``True`` (it needs ``resize_crop`` too) lets ``"images"`` be a ``PngBatch`` (``collate_fn=collate_png``),
+    decoded by the two launches of ``basd_amd.png.PngDecoder`` ahead of the resize launch; ``False``: no decoder.
     ``max_grad_norm`` (``None`` or a finite number > 0) and ``skip_nonfinite``: global-norm clipping and the guard against
     inf / NaN gradients of ``AdamWScheduleFree``, decided on the device inside the optimizer's two launches (they need
     ``optimizer="schedulefree"``).  The norm is taken over the student's and the loss's gradients together, after the
@@ -127,7 +129,7 @@ class Trainer:
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
-                 resize_crop: bool = False, jpeg_decode=False, max_grad_norm=None,
+                 resize_crop: bool = False, jpeg_decode=False, png_decode: bool = False, max_grad_norm=None,
                  skip_nonfinite: bool = False, prefetch: int = 0) -> None:
         if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
             raise ValueError(f"prefetch must be an int >= 0 (got {prefetch!r})")
@@ -203,6 +205,15 @@ class Trainer:
                                  "resize launch takes); got resize_crop=False")
             from .jpeg import JpegDecoder
             self._decoder = JpegDecoder(self.device, entropy="parallel" if jpeg_decode == "parallel" else "serial")
+        self._png_decoder = None
+        if not isinstance(png_decode, bool):
+            raise ValueError(f"png_decode must be True or False, not {png_decode!r}")
+        if png_decode:
+            if not resize_crop:
+                raise ValueError("png_decode needs resize_crop=True (the decoded images are a ragged batch, which the "
+                                 "resize launch takes); got resize_crop=False")
+            from .png import PngDecoder
+            self._png_decoder = PngDecoder(self.device)
         from .prefetch import DevicePrefetcher
         self.prefetch = prefetch
         self._prefetcher = DevicePrefetcher(self.prepare_batch, device=self.device, depth=prefetch)
@@ -247,6 +258,10 @@ class Trainer:
             from .jpeg import JpegBatch
             if isinstance(images, JpegBatch):
                 images = self._decoder(images.to(dev, non_blocking=True))
+        if self._png_decoder is not None:
+            from .png import PngBatch
+            if isinstance(images, PngBatch):
+                images = self._png_decoder(images.to(dev, non_blocking=True))
         if not isinstance(images, RaggedBatch):
             raise TypeError("resize_crop works on decoded images (the loader decodes, nothing else): the batch needs "
                             f"'images', a RaggedBatch (collate_fn=collate_ragged); got {sorted(batch)}")
@@ -376,7 +391,7 @@ class Trainer:
         ``pixel_values``: they are normalised on the device with the ``augmented`` statistics -- the dataset's own, which
         the reference's validation loader uses too (datasets.py:168-175) -- and written as ``mix_dtype``.  With
         ``resize_crop`` it may hand over ``images`` (a ``RaggedBatch``) instead: they are resized and cropped first (with
-        ``jpeg_decode`` a ``JpegBatch``: decoded, then resized and cropped).  Has the
+        ``jpeg_decode`` a ``JpegBatch``, with ``png_decode`` a ``PngBatch``: decoded, then resized and cropped).  Has the
         signature ``train(..., evaluate=)`` expects: ``trainer.train(train_loader, val_loader,
         evaluate=trainer.evaluate)``."""
         from .evaluation import evaluate_model
@@ -384,7 +399,8 @@ class Trainer:
         stats = None if self.image_stats is None else self.image_stats["augmented"]
         return evaluate_model(model, val_loader, self.criterion, num_classes=self.config.model.num_classes,
                               distributed=distributed, image_stats=stats, input_dtype=self.mix_dtype,
-                              resize_crop=self._resizer, jpeg_decode=self._decoder, prefetch=self.prefetch,
+                              resize_crop=self._resizer, jpeg_decode=self._decoder, png_decode=self._png_decoder,
+                              prefetch=self.prefetch,
                               prefetch_stream=self._prefetcher.stream)
 
     def train(self, train_loader, val_loader=None, start_epoch: int = 0, *, evaluate=None, on_epoch_end=None) -> dict:
