@@ -1002,6 +1002,7 @@ int basd_resize_crop(const unsigned char* src, long src_bytes, unsigned char* ds
 
 #define BASD_JPEG_KIND_STREAM 0      /* a baseline JPEG stream, decoded on the device */
 #define BASD_JPEG_KIND_RAW 1         /* width * height * 3 RGB bytes made by the host fallback, copied into place */
+#define BASD_JPEG_KIND_PROGRESSIVE 2 /* a progressive JPEG stream: basd_jpeg_decode_progressive only (BAD_RECORD elsewhere) */
 
 /* The per-image status word (0: decoded); the batch's status word is the OR of 1 << (code - 1). */
 #define BASD_JPEG_BAD_RECORD 1       /* a field of the record outside its bounds (nothing of the image is read) */
@@ -1028,7 +1029,10 @@ typedef struct BasdJpegRecord {
     int n_seg;                    /* entropy-coded segments: 1, or ceil(MCUs / restart) */
     int quant[3];                 /* per component: offset of the 64 bytes of its DQT table (zigzag order) */
     int dc[3], ac[3];             /* per component: offset of its DHT table (16 counts, then the values) */
-    int pad[4];
+    int n_scans;                  /* BASD_JPEG_KIND_PROGRESSIVE: scans, 1 .. BASD_JPEG_MAX_SCANS; else unused */
+    int scan_offset;              /* ... the n_scans BasdJpegScan rows, counted from src_offset (8-byte aligned in the buffer) */
+    int scan_segments;            /* ... the largest n_seg of a scan (the host's summary; the rows are what is checked) */
+    int pad;
 } BasdJpegRecord;
 
 /* Bytes at the start of the workspace that hold the B per-image status words. */
@@ -1146,6 +1150,82 @@ int basd_jpeg_decode(const unsigned char* src, long src_bytes, unsigned char* ou
 int basd_jpeg_decode_parallel(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
                               const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status,
                               long max_blocks, long max_pixels, int sub_bytes, hipStream_t stream);
+
+/* ---- progressive JPEG streams in the same batch (opt-in): one more launch ------------------------------------- */
+
+#define BASD_JPEG_MAX_SCANS 64       /* scans of a progressive stream the device takes (more: the host fallback) */
+
+/* One row of a progressive record's scan table (64 bytes; the table sits in the byte buffer at src_offset +
+ * scan_offset).  Offsets are counted from src_offset. */
+typedef struct BasdJpegScan {
+    int seg_offset;               /* n_seg int32 (4-byte aligned in the buffer): the first entropy-coded byte of every segment */
+    int n_seg;                    /* 1, or ceil(scan units / restart) */
+    int data_end;                 /* where the scan's data ends: the marker behind it, or src_len */
+    int restart;                  /* scan units per restart interval in force at this SOS, 0: none */
+    int ncomp;                    /* 1 (a one-component scan), or the frame's (an interleaved DC scan) */
+    int comp;                     /* the frame index of a one-component scan's component */
+    int ss, se, ah, al;           /* the band and the successive approximation: ss = se = 0 or 1 <= ss <= se <= 63; al <= 13 */
+    int level;                    /* 0, or 1 + the largest level of an earlier scan that shares a component and overlaps
+                                     in ss .. se; below n_scans */
+    int dc[3];                    /* DC first scans: per FRAME component of the scan the offset of its DHT table */
+    int ac;                       /* AC scans: the offset of the DHT table */
+    int pad;
+} BasdJpegScan;
+
+/* Decodes a batch that may hold records of kind BASD_JPEG_KIND_PROGRESSIVE next to baseline and raw ones.  Arguments,
+ * checks, workspace layout (192 bytes per block of the MCU-padded frame), status words and BASD_EINVAL rules are those
+ * of basd_jpeg_decode_parallel; `parallel` picks the baseline entropy stage (0: that of basd_jpeg_decode, 1: that of
+ * basd_jpeg_decode_parallel with `sub_bytes`; sub_bytes must be 0 with parallel == 0); max_scans / max_segments: the
+ * largest scan count of a progressive record and the largest segment count of a scan of the batch (0 .. BASD_JPEG_MAX_SCANS
+ * and >= 0; a record or a scan that claims more is BASD_JPEG_BAD_RECORD).
+ *
+ * Scope: SOF2, Huffman coding, and everything else of the frame as above (8 bits, 1 or 3 components, the same sampling,
+ * 8-bit DQT tables all ahead of the first SOS, no Adobe segment, the JFIF / component-id rule, no DNL); at most
+ * BASD_JPEG_MAX_SCANS scans with only DHT, DRI, COM and APPn segments between them; a DC scan (ss = se = 0) of all
+ * components in frame order or of one, an AC scan (1 <= ss <= se <= 63) of one, behind that component's first DC
+ * scan; al <= 13; the first scan of a coefficient has ah = 0, every later one ah = the previous al and al = ah - 1;
+ * and the progression is COMPLETE: at EOI every coefficient of every component has been coded down to al = 0 (libjpeg
+ * smooths the blocks of an incomplete one, which this text does not describe).  The host decides all of this
+ * (basd_amd.jpeg.parse_jpeg(data, progressive=True)) and sends every other file through the fallback.
+ *
+ * Specification.  Coefficients are int16, zero before the first scan; what is stored wraps to 16 bits.
+ * Geometry: an interleaved scan walks the frame's MCUs as the baseline scan does.  A one-component scan walks that
+ * component's own blocks in raster order over ceil(cw / 8) x ceil(ch / 8), cw = ceil(W h / hmax), ch = ceil(H v / vmax):
+ * NOT the MCU-padded grid (a 17 x 33 4:2:0 file: 3 x 5 luma blocks, not 4 x 6).  A scan unit is an MCU or such a block.
+ * Restart segments: with DRI in force at the scan's SOS a segment is `restart` scan units, RSTn as above; at a segment's
+ * start the DC predictors and EOBRUN are 0.  Tables are the ones in force at the SOS.
+ * DC first (ss = 0, ah = 0): the DC symbol s, pred += EXTEND(s bits), coefficient 0 = pred << al.
+ * DC refinement (ss = 0, ah > 0): one bit; if it is 1, coefficient 0 |= 1 << al.
+ * AC first (ah = 0): if EOBRUN > 0: EOBRUN -= 1, the block is done.  Else k = ss; while k <= se: the AC symbol rs,
+ *   r = rs >> 4, s = rs & 15; s != 0: k += r, coefficient k = EXTEND(s bits) * 2^al, k += 1; s == 0 and r == 15:
+ *   k += 16; otherwise EOBRUN = 2^r - 1, plus r more bits where r > 0, and the block is done.
+ * AC refinement (ah > 0), p1 = 1 << al, m1 = -1 << al; "correct k": read one bit; if it is 1 and (coefficient k & p1)
+ *   == 0, add p1 where the coefficient is >= 0, else m1.  k = ss.  If EOBRUN == 0, while k <= se: read rs; s != 0: s
+ *   must be 1, one bit, the new value is p1 if it is 1, else m1; s == 0 and r != 15: EOBRUN = 2^r, plus r bits where
+ *   r > 0, leave the loop; then walk: while k <= se: coefficient k non-zero: correct k; zero: r -= 1, stop the walk
+ *   where r < 0; k += 1.  Behind the walk a new value is stored at k; k += 1.  Then, if EOBRUN > 0: every non-zero
+ *   coefficient from k to se is corrected, EOBRUN -= 1.
+ * Dequantisation, IDCT, upsampling and colour are the text above, unchanged.
+ * Errors: a value to be stored at k > se is BASD_JPEG_BAD_INDEX; a refinement symbol with s > 1 BASD_JPEG_BAD_CODE; a
+ * DC category above 15 or a DC predictor outside 16 bits BASD_JPEG_BAD_VALUE; a scan's segment count that is not its
+ * grid's BASD_JPEG_BAD_RESTART; the codes above otherwise.  An image's status is the code of the FIRST SCAN IN STREAM
+ * ORDER that has a failing segment, and where several segments of that scan fail the largest of their codes (every
+ * segment of a scan that runs is decoded); scans behind it do not matter.  A failed image's output is all zero.
+ *
+ * Launches (FOUR, whatever B; no allocation, no memset, no wait):
+ *   progressive  one workgroup of 512 lanes per image, which returns at once for the other kinds.  The record and EVERY
+ *                scan row are checked against the buffers before anything they name is read; the coefficient area is
+ *                zeroed; then the scans run by levels with a barrier between levels: scans of one level touch disjoint
+ *                coefficients, the n-th of them goes to wave n mod 8 (scans of different kinds diverge, so they do not
+ *                share a wave), and within a scan lane l of the wave decodes segments l, l + 64, ...  Coefficients are
+ *                read and written in place, at the block's position in the INTERLEAVED order, which is what idct reads.
+ *                Once a segment of scan j has failed, no scan behind j is begun; scans ahead of j still run.
+ *   entropy      the chosen baseline stage; it passes over progressive records and leaves their status words alone;
+ *   idct, pixels as above; they take a progressive record as they take a stream. */
+int basd_jpeg_decode_progressive(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
+                                 const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status,
+                                 long max_blocks, long max_pixels, int sub_bytes, int parallel, int max_scans,
+                                 int max_segments, hipStream_t stream);
 
 /* ---- Pillow-exact 8-bit PNG decoding of a batch of files in two launches ------------------------------------ */
 

@@ -18,7 +18,8 @@ Sub-modules:
   ``resize``   ``ResizeCrop`` / ``pack_images`` / ``collate_ragged`` / ``draw_crop_params``: Pillow-exact crops and resizes
                of ragged batches of decoded uint8 images, both views in one launch
   ``jpeg``     ``JpegDecoder`` / ``pack_jpegs`` / ``collate_jpeg`` / ``parse_jpeg``: Pillow-exact baseline JPEG decoding of a
-               batch of files' bytes into a ragged batch, three launches per batch
+               batch of files' bytes into a ragged batch, three launches per batch (progressive files too, opt-in
+               with ``progressive=True`` where the batch is packed: one more launch)
   ``png``      ``PngDecoder`` / ``pack_pngs`` / ``collate_png`` / ``parse_png``: Pillow-exact 8-bit PNG decoding of a batch of
                files' bytes into a ragged batch, two launches per batch
   ``prefetch``  ``DevicePrefetcher``: the input work of the next batch on a side stream while the step runs

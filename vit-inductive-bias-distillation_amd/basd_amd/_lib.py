@@ -131,6 +131,7 @@ SIGNATURES = {
     "basd_jpeg_status_bytes": [i32],
     "basd_jpeg_decode": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp],
     "basd_jpeg_decode_parallel": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, i32, vp],
+    "basd_jpeg_decode_progressive": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp],
     "basd_png_status_bytes": [i32],
     "basd_png_decode": [vp, i64, vp, i64, i32, vp, vp, i64, vp, i64, i64, vp],
 }

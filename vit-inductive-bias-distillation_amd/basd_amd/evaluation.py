@@ -125,7 +125,8 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
     images, ``collate_fn=collate_ragged``) instead of ``pixel_values``: one launch makes the clean view (``Resize ->
     CenterCrop``), which then takes the uint8 path above, so ``image_stats`` is needed (``ValueError`` otherwise).
     ``jpeg_decode``: a ``basd_amd.jpeg.JpegDecoder`` (it needs ``resize_crop``); with it ``images`` may be a ``JpegBatch``
-    of the files' bytes (``collate_fn=collate_jpeg``), decoded on the device ahead of the resize launch.
+    of the files' bytes (``collate_fn=collate_jpeg``), decoded on the device ahead of the resize launch (progressive files
+    too where the batch was packed with ``collate_jpeg(..., progressive=True)``: the choice is the collate function's).
     ``png_decode``: a ``basd_amd.png.PngDecoder``, the same for a ``PngBatch`` (``collate_fn=collate_png``).
     ``prefetch``: an int >= 0 (``ValueError`` otherwise); the input half of up to that many batches (transfer, decode,
     resize, conversion, labels) runs ahead on a side stream (``basd_amd.prefetch.DevicePrefetcher``) while the model

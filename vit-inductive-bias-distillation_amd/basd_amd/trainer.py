@@ -107,7 +107,10 @@ class Trainer:
     (the loader does not decode, ``collate_fn=collate_jpeg``): three launches of ``basd_amd.jpeg.JpegDecoder`` decode it
     into the ``RaggedBatch`` the resize launch takes; a ``RaggedBatch`` is taken as before.  ``"parallel"`` is ``True`` with
     ``JpegDecoder(entropy="parallel")``: the entropy stage decodes inside a segment with a workgroup's lanes instead of
-    one lane per segment (the same bytes; what it gains is in DESIGN.md section 8).  ``False``: no decoder.
+    one lane per segment (the same bytes; what it gains is in DESIGN.md section 8).  ``False``: no decoder.  Whether
+    progressive files are decoded on the device too is no option here: it is chosen where the batch is packed
+    (``collate_fn=functools.partial(collate_jpeg, progressive=True)``), and the decoder follows the batch with one more
+    launch.
     ``png_decode``: ``True`` (it needs ``resize_crop`` too) lets ``"images"`` be a ``PngBatch`` (``collate_fn=collate_png``),
     decoded by the two launches of ``basd_amd.png.PngDecoder`` ahead of the resize launch; ``False``: no decoder.
     ``max_grad_norm`` (``None`` or a finite number > 0) and ``skip_nonfinite``: global-norm clipping and the guard against

@@ -12,6 +12,8 @@
 //             in registers, 8 stores of 8 bytes into the component plane.
 //   pixels    one lane per pixel (grid: pixels x images): up to four chroma taps per plane, the colour formula, three
 //             byte stores; a raw record's pixels are copied from the byte buffer; a failed image is zeroed.
+// basd_jpeg_decode_parallel swaps the entropy kernel for one that works inside a segment; basd_jpeg_decode_progressive
+// puts one launch ahead of the three, which decodes the scans of progressive records (both further down).
 #include "basd_common.h"
 #include "jpeg_core.h"
 
@@ -35,12 +37,16 @@ struct JpegArgs {
     int* status;
 };
 
+// kMixed: the batch may hold progressive records, which jpeg_progressive_kernel has decoded: they are passed over and
+// their status words left alone (basd_jpeg_decode_progressive).  Without it such a record is a bad record.
+template <bool kMixed>
 __global__ void __launch_bounds__(kJpegLanes) jpeg_entropy_kernel(JpegArgs a) {
     __shared__ JpegHuff tables[6];
     __shared__ uint32_t blocks[kJpegLanes * kJpegBlockPitch];
     __shared__ int failed;
     const int lane = threadIdx.x, img = blockIdx.x;
     const BasdJpegRecord r = a.table[img];
+    if (kMixed && r.kind == BASD_JPEG_KIND_PROGRESSIVE) return;        // uniform over the workgroup
     int* image_status = (int*)a.ws + img;
     int bad = jpeg_check_record(r, a.src_bytes, a.out_bytes, a.ws_bytes, a.ws_reserved);
     JpegGeometry g = {};
@@ -87,7 +93,7 @@ __global__ void __launch_bounds__(kJpegIdctBlock) jpeg_idct_kernel(JpegArgs a) {
     const int img = blockIdx.y;
     if (((const int*)a.ws)[img] != 0) return;                          // the record is only followed where it was admitted
     const BasdJpegRecord r = a.table[img];
-    if (r.kind != BASD_JPEG_KIND_STREAM) return;
+    if (r.kind != BASD_JPEG_KIND_STREAM && r.kind != BASD_JPEG_KIND_PROGRESSIVE) return;
     const JpegGeometry g = jpeg_geometry(r);
     const long blk = (long)blockIdx.x * kJpegIdctBlock + threadIdx.x;
     if (blk >= g.blocks) return;
@@ -278,6 +284,7 @@ __device__ int jpeg_segment_parallel(const BasdJpegRecord& r, const JpegGeometry
     return BASD_JPEG_TRUNCATED;
 }
 
+template <bool kMixed>                                                 // as in jpeg_entropy_kernel
 __global__ void __launch_bounds__(kJpegParLanes) jpeg_entropy_parallel_kernel(JpegArgs a, int sub_bytes) {
     __shared__ JpegHuff tables[6];
     __shared__ uint32_t blocks[kJpegLanes * kJpegBlockPitch];
@@ -285,6 +292,7 @@ __global__ void __launch_bounds__(kJpegParLanes) jpeg_entropy_parallel_kernel(Jp
     __shared__ int failed;
     const int lane = threadIdx.x, img = blockIdx.x;
     const BasdJpegRecord r = a.table[img];
+    if (kMixed && r.kind == BASD_JPEG_KIND_PROGRESSIVE) return;        // uniform over the workgroup
     int* image_status = (int*)a.ws + img;
     int bad = jpeg_check_record(r, a.src_bytes, a.out_bytes, a.ws_bytes, a.ws_reserved);
     JpegGeometry g = {};
@@ -336,7 +344,166 @@ __global__ void __launch_bounds__(kJpegParLanes) jpeg_entropy_parallel_kernel(Jp
     }
 }
 
+// ---- progressive streams (basd_jpeg_decode_progressive; the scheme is in include/basd_hip.h) ----------------------------
+// One workgroup of kJpegProgWaves waves per image.  The record and every row of its scan table are checked first; the
+// rows then live in LDS.  The scans run level by level: scans of one level touch disjoint coefficients, so they run at
+// the same time, kJpegProgWaves of them in a round, the n-th to wave n (scans of different kinds would serialise in one
+// wave), and lane l of the wave takes the scan's segments l, l + 64, ...  Coefficients are read and written in place in
+// the workspace; the barrier behind a round orders them for the next level's readers.  Every barrier is reached by
+// every lane: what a round does depends on the rows in LDS alone.
+constexpr int kJpegProgWaves = 8;                                    // Pillow's script has 5 scans in its first level, the
+                                                                       // hand-made ones of the tests up to 7: one round each
+constexpr int kJpegProgLanes = 64 * kJpegProgWaves;
+
+struct JpegProgShared {
+    JpegHuff tables[kJpegProgWaves][3];
+    BasdJpegScan scans[BASD_JPEG_MAX_SCANS];
+    int code[BASD_JPEG_MAX_SCANS];                                     // per scan: the largest code of its segments
+    int failed_scan;                                                   // the first scan in stream order that failed
+    int bad_rows, levels;
+};
+static_assert(sizeof(BasdJpegScan) == 64, "the scan table has 64-byte rows");
+static_assert(sizeof(JpegProgShared) <= 48 * 1024, "three images share a CU's LDS");
+
+__global__ void __launch_bounds__(kJpegProgLanes) jpeg_progressive_kernel(JpegArgs a, int max_scans, int max_segments) {
+    __shared__ JpegProgShared sh;
+    const int lane = threadIdx.x, in_wave = lane & 63, wave = lane >> 6, img = blockIdx.x;
+    const BasdJpegRecord r = a.table[img];
+    if (r.kind != BASD_JPEG_KIND_PROGRESSIVE) return;                  // uniform: the baseline stage's, or raw
+    int* image_status = (int*)a.ws + img;
+    const int bad = jpeg_check_progressive(r, a.src_bytes, a.out_bytes, a.ws_bytes, a.ws_reserved, max_scans);
+    if (bad) {                                                         // uniform
+        if (lane == 0) {
+            *image_status = bad;
+            atomicOr(a.status, 1 << (bad - 1));
+        }
+        return;
+    }
+    if (lane == 0) {
+        sh.failed_scan = r.n_scans;
+        sh.bad_rows = sh.levels = 0;
+    }
+    __syncthreads();
+    if (lane < r.n_scans) {                                            // n_scans <= 64: one row per lane of wave 0
+        BasdJpegScan s;
+        __builtin_memcpy(&s, __builtin_assume_aligned(a.src + r.src_offset + r.scan_offset + 64L * lane, 8), 64);
+        if (jpeg_check_scan(r, s, a.src_bytes, max_segments)) atomicMax(&sh.levels, s.level + 1);
+        else atomicOr(&sh.bad_rows, 1);
+        sh.scans[lane] = s;
+        sh.code[lane] = 0;
+    }
+    __syncthreads();
+    if (sh.bad_rows) {                                                 // uniform: no row is followed
+        if (lane == 0) {
+            *image_status = BASD_JPEG_BAD_RECORD;
+            atomicOr(a.status, 1 << (BASD_JPEG_BAD_RECORD - 1));
+        }
+        return;
+    }
+    const JpegGeometry g = jpeg_geometry(r);
+    short* coef = (short*)(a.ws + r.coef_offset);
+    for (long i = lane; i < g.blocks * 8; i += kJpegProgLanes) ((uint4*)coef)[i] = make_uint4(0, 0, 0, 0);
+    __syncthreads();                                                   // the zeros are ahead of every coefficient
+    const unsigned char* stream = a.src + r.src_offset;
+    const int levels = sh.levels;
+    for (int level = 0; level < levels; ++level) {
+        for (int next = 0;;) {                                         // a round: the next kJpegProgWaves scans of the level
+            int mine = -1, found = 0;
+            for (; next < r.n_scans && found < kJpegProgWaves; ++next)
+                if (sh.scans[next].level == level) {
+                    if (found == wave) mine = next;
+                    ++found;
+                }
+            if (found == 0) break;                                     // uniform
+            // behind a failure in scan j only scans ahead of j may still matter
+            const bool run = mine >= 0 && mine < sh.failed_scan;
+            JpegHuff* tables = sh.tables[wave];
+            if (run && in_wave < 3) {
+                const BasdJpegScan& s = sh.scans[mine];
+                bool ok = true;
+                if (s.ss == 0 && s.ah == 0) {
+                    if (in_wave < r.ncomp && (s.ncomp > 1 || in_wave == s.comp))
+                        ok = jpeg_build_huff(stream, r.src_len, jpeg_pick(s.dc, in_wave), &tables[in_wave]);
+                } else if (s.ss > 0 && in_wave == 0) {
+                    ok = jpeg_build_huff(stream, r.src_len, s.ac, &tables[0]);
+                }
+                if (!ok) atomicMax(&sh.code[mine], BASD_JPEG_BAD_TABLE);
+            }
+            __syncthreads();                                           // failed_scan is written behind here, read ahead
+            if (run && sh.code[mine] != 0) {                           // uniform over the wave: a bad table
+                if (in_wave == 0) atomicMin(&sh.failed_scan, mine);
+            } else if (run) {
+                const BasdJpegScan s = sh.scans[mine];
+                int row;
+                if (!jpeg_scan_segments_ok(s, jpeg_scan_units(r, g, s, row))) {
+                    if (in_wave == 0) {
+                        atomicMax(&sh.code[mine], BASD_JPEG_BAD_RESTART);
+                        atomicMin(&sh.failed_scan, mine);
+                    }
+                } else {
+                    for (int seg = in_wave; seg < s.n_seg; seg += 64) {
+                        const int code = jpeg_scan_segment(r, g, s, a.src, seg, tables, coef);
+                        if (code) {                                    // the scan's other segments are still decoded
+                            atomicMax(&sh.code[mine], code);
+                            atomicMin(&sh.failed_scan, mine);
+                        }
+                    }
+                }
+            }
+            __syncthreads();                                           // the round's coefficients are ahead of the next reader
+        }
+    }
+    if (lane == 0) {
+        const int failed = sh.failed_scan < r.n_scans ? sh.code[sh.failed_scan] : 0;
+        *image_status = failed;
+        if (failed) atomicOr(a.status, 1 << (failed - 1));
+    }
+}
+
 }  // namespace basd
+
+namespace {
+
+// The argument rules shared by the three entry points, and the launches' common argument.
+int jpeg_arguments(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
+                   const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status, long max_blocks,
+                   long max_pixels, basd::JpegArgs& a) {
+    BASD_CHECK_ARG(B >= 0 && B <= BASD_JPEG_MAX_BATCH && src_bytes >= 0 && out_bytes >= 0 && ws_bytes >= 0 &&
+                   max_blocks >= 0 && max_pixels >= 0);
+    if (B == 0) return BASD_OK;
+    BASD_CHECK_ARG(src && out && table && ws && status);
+    BASD_CHECK_ARG((src_bytes & 15) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)ws & 15) == 0);
+    const long reserved = basd_jpeg_status_bytes(B);
+    BASD_CHECK_ARG(ws_bytes >= reserved);
+    const long side = BASD_JPEG_MAX_SIDE;
+    BASD_CHECK_ARG(max_pixels <= side * side && max_blocks <= 3 * (side / 8 + 1) * (side / 8 + 1));
+    const uintptr_t lo[3] = {(uintptr_t)src, (uintptr_t)out, (uintptr_t)ws};
+    const uintptr_t hi[3] = {lo[0] + (uintptr_t)src_bytes, lo[1] + (uintptr_t)out_bytes, lo[2] + (uintptr_t)ws_bytes};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j) BASD_CHECK_ARG(hi[i] <= lo[j] || hi[j] <= lo[i]);
+    a = basd::JpegArgs{};
+    a.src = src; a.src_bytes = src_bytes; a.out = out; a.out_bytes = out_bytes; a.table = table;
+    a.ws = ws; a.ws_bytes = ws_bytes; a.ws_reserved = reserved; a.status = status;
+    return BASD_OK;
+}
+
+bool jpeg_sub_bytes_ok(int sub_bytes) {
+    return sub_bytes == 0 ||
+           (sub_bytes >= BASD_JPEG_SUB_BYTES_MIN && sub_bytes <= BASD_JPEG_SUB_BYTES_MAX && (sub_bytes & 7) == 0);
+}
+
+// The two launches behind every entropy stage (always both: a batch of raw records alone has no blocks: one idle
+// workgroup per image).
+void jpeg_idct_and_pixels(const basd::JpegArgs& a, int B, long max_blocks, long max_pixels, hipStream_t stream) {
+    const long idct_groups = (max_blocks + basd::kJpegIdctBlock - 1) / basd::kJpegIdctBlock;
+    const long pixel_groups = (max_pixels + basd::kJpegPixelBlock - 1) / basd::kJpegPixelBlock;
+    basd::jpeg_idct_kernel<<<dim3((unsigned)(idct_groups > 0 ? idct_groups : 1), (unsigned)B), basd::kJpegIdctBlock, 0,
+                             stream>>>(a);
+    basd::jpeg_pixel_kernel<<<dim3((unsigned)(pixel_groups > 0 ? pixel_groups : 1), (unsigned)B), basd::kJpegPixelBlock,
+                              0, stream>>>(a);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -345,63 +512,45 @@ long basd_jpeg_status_bytes(int B) { return B < 0 ? 0 : ((long)B * 4 + 127) & ~1
 int basd_jpeg_decode(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
                      const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status, long max_blocks,
                      long max_pixels, hipStream_t stream) {
-    BASD_CHECK_ARG(B >= 0 && B <= BASD_JPEG_MAX_BATCH && src_bytes >= 0 && out_bytes >= 0 && ws_bytes >= 0 &&
-                   max_blocks >= 0 && max_pixels >= 0);
+    basd::JpegArgs a;
+    BASD_TRY(jpeg_arguments(src, src_bytes, out, out_bytes, B, table, ws, ws_bytes, status, max_blocks, max_pixels, a));
     if (B == 0) return BASD_OK;
-    BASD_CHECK_ARG(src && out && table && ws && status);
-    BASD_CHECK_ARG((src_bytes & 15) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)ws & 15) == 0);
-    const long reserved = basd_jpeg_status_bytes(B);
-    BASD_CHECK_ARG(ws_bytes >= reserved);
-    const long side = BASD_JPEG_MAX_SIDE;
-    BASD_CHECK_ARG(max_pixels <= side * side && max_blocks <= 3 * (side / 8 + 1) * (side / 8 + 1));
-    const uintptr_t lo[3] = {(uintptr_t)src, (uintptr_t)out, (uintptr_t)ws};
-    const uintptr_t hi[3] = {lo[0] + (uintptr_t)src_bytes, lo[1] + (uintptr_t)out_bytes, lo[2] + (uintptr_t)ws_bytes};
-    for (int i = 0; i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j) BASD_CHECK_ARG(hi[i] <= lo[j] || hi[j] <= lo[i]);
-    basd::JpegArgs a = {};
-    a.src = src; a.src_bytes = src_bytes; a.out = out; a.out_bytes = out_bytes; a.table = table;
-    a.ws = ws; a.ws_bytes = ws_bytes; a.ws_reserved = reserved; a.status = status;
-    basd::jpeg_entropy_kernel<<<(unsigned)B, basd::kJpegLanes, 0, stream>>>(a);
-    // always three launches (a batch of raw records alone has no blocks: one idle workgroup per image)
-    const long idct_groups = (max_blocks + basd::kJpegIdctBlock - 1) / basd::kJpegIdctBlock;
-    const long pixel_groups = (max_pixels + basd::kJpegPixelBlock - 1) / basd::kJpegPixelBlock;
-    basd::jpeg_idct_kernel<<<dim3((unsigned)(idct_groups > 0 ? idct_groups : 1), (unsigned)B), basd::kJpegIdctBlock, 0,
-                             stream>>>(a);
-    basd::jpeg_pixel_kernel<<<dim3((unsigned)(pixel_groups > 0 ? pixel_groups : 1), (unsigned)B), basd::kJpegPixelBlock,
-                              0, stream>>>(a);
+    basd::jpeg_entropy_kernel<false><<<(unsigned)B, basd::kJpegLanes, 0, stream>>>(a);
+    jpeg_idct_and_pixels(a, B, max_blocks, max_pixels, stream);
     BASD_RETURN_LAST();
 }
 
 int basd_jpeg_decode_parallel(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
                               const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status,
                               long max_blocks, long max_pixels, int sub_bytes, hipStream_t stream) {
-    BASD_CHECK_ARG(B >= 0 && B <= BASD_JPEG_MAX_BATCH && src_bytes >= 0 && out_bytes >= 0 && ws_bytes >= 0 &&
-                   max_blocks >= 0 && max_pixels >= 0);
-    BASD_CHECK_ARG(sub_bytes == 0 || (sub_bytes >= BASD_JPEG_SUB_BYTES_MIN && sub_bytes <= BASD_JPEG_SUB_BYTES_MAX &&
-                                      (sub_bytes & 7) == 0));
+    basd::JpegArgs a;
+    BASD_CHECK_ARG(B >= 0 && jpeg_sub_bytes_ok(sub_bytes));
+    BASD_TRY(jpeg_arguments(src, src_bytes, out, out_bytes, B, table, ws, ws_bytes, status, max_blocks, max_pixels, a));
     if (B == 0) return BASD_OK;
-    BASD_CHECK_ARG(src && out && table && ws && status);
-    BASD_CHECK_ARG((src_bytes & 15) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)ws & 15) == 0);
-    const long reserved = basd_jpeg_status_bytes(B);
-    BASD_CHECK_ARG(ws_bytes >= reserved);
-    const long side = BASD_JPEG_MAX_SIDE;
-    BASD_CHECK_ARG(max_pixels <= side * side && max_blocks <= 3 * (side / 8 + 1) * (side / 8 + 1));
-    const uintptr_t lo[3] = {(uintptr_t)src, (uintptr_t)out, (uintptr_t)ws};
-    const uintptr_t hi[3] = {lo[0] + (uintptr_t)src_bytes, lo[1] + (uintptr_t)out_bytes, lo[2] + (uintptr_t)ws_bytes};
-    for (int i = 0; i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j) BASD_CHECK_ARG(hi[i] <= lo[j] || hi[j] <= lo[i]);
-    basd::JpegArgs a = {};
-    a.src = src; a.src_bytes = src_bytes; a.out = out; a.out_bytes = out_bytes; a.table = table;
-    a.ws = ws; a.ws_bytes = ws_bytes; a.ws_reserved = reserved; a.status = status;
-    basd::jpeg_entropy_parallel_kernel<<<(unsigned)B, basd::kJpegParLanes, 0, stream>>>(
+    basd::jpeg_entropy_parallel_kernel<false><<<(unsigned)B, basd::kJpegParLanes, 0, stream>>>(
         a, sub_bytes ? sub_bytes : basd::kJpegParSubBytes);
-    // the other two launches are those of basd_jpeg_decode
-    const long idct_groups = (max_blocks + basd::kJpegIdctBlock - 1) / basd::kJpegIdctBlock;
-    const long pixel_groups = (max_pixels + basd::kJpegPixelBlock - 1) / basd::kJpegPixelBlock;
-    basd::jpeg_idct_kernel<<<dim3((unsigned)(idct_groups > 0 ? idct_groups : 1), (unsigned)B), basd::kJpegIdctBlock, 0,
-                             stream>>>(a);
-    basd::jpeg_pixel_kernel<<<dim3((unsigned)(pixel_groups > 0 ? pixel_groups : 1), (unsigned)B), basd::kJpegPixelBlock,
-                              0, stream>>>(a);
+    jpeg_idct_and_pixels(a, B, max_blocks, max_pixels, stream);
+    BASD_RETURN_LAST();
+}
+
+int basd_jpeg_decode_progressive(const unsigned char* src, long src_bytes, unsigned char* out, long out_bytes, int B,
+                                 const BasdJpegRecord* table, unsigned char* ws, long ws_bytes, int* status,
+                                 long max_blocks, long max_pixels, int sub_bytes, int parallel, int max_scans,
+                                 int max_segments, hipStream_t stream) {
+    basd::JpegArgs a;
+    BASD_CHECK_ARG(B >= 0 && (parallel == 0 || parallel == 1) && jpeg_sub_bytes_ok(sub_bytes) &&
+                   (parallel || sub_bytes == 0));
+    BASD_CHECK_ARG(max_scans >= 0 && max_scans <= BASD_JPEG_MAX_SCANS && max_segments >= 0);
+    BASD_TRY(jpeg_arguments(src, src_bytes, out, out_bytes, B, table, ws, ws_bytes, status, max_blocks, max_pixels, a));
+    if (B == 0) return BASD_OK;
+    // four launches: the progressive records' coefficients, the others' (which leaves those alone), idct, pixels
+    basd::jpeg_progressive_kernel<<<(unsigned)B, basd::kJpegProgLanes, 0, stream>>>(a, max_scans, max_segments);
+    if (parallel)
+        basd::jpeg_entropy_parallel_kernel<true><<<(unsigned)B, basd::kJpegParLanes, 0, stream>>>(
+            a, sub_bytes ? sub_bytes : basd::kJpegParSubBytes);
+    else
+        basd::jpeg_entropy_kernel<true><<<(unsigned)B, basd::kJpegLanes, 0, stream>>>(a);
+    jpeg_idct_and_pixels(a, B, max_blocks, max_pixels, stream);
     BASD_RETURN_LAST();
 }
 

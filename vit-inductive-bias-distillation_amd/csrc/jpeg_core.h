@@ -1,7 +1,7 @@
 // The per-image arithmetic of the JPEG decoder (specification: include/basd_hip.h) as host + device functions: the
-// record check, the Huffman tables, the bit reader, one entropy-coded segment, the block IDCT, the upsampling taps and
-// the colour formula.  csrc/jpeg.hip wraps them in three kernels; tools/jpeg_host_check.cpp compiles the same text for
-// the host and runs it under the sanitizers.  Nothing here allocates, and nothing reads or writes outside the ranges
+// record check, the Huffman tables, the bit reader, one entropy-coded segment, the four kinds of progressive scan, the
+// block IDCT, the upsampling taps and the colour formula.  csrc/jpeg.hip wraps them in kernels; tools/jpeg_host_check.cpp
+// (and tools/jpeg_progressive_host_check.cpp) compile the same text for the host and run it under the sanitizers.  Nothing here allocates, and nothing reads or writes outside the ranges
 // the record check has admitted.
 #pragma once
 #include <stdint.h>
@@ -62,31 +62,42 @@ BASD_HD bool jpeg_out_ok(const BasdJpegRecord& r, long out_bytes) {
     return r.out_offset >= 0 && r.out_offset <= out_bytes && n <= out_bytes - r.out_offset;
 }
 
-// Every field of a record against the three buffers: 0, or BASD_JPEG_BAD_RECORD.
-BASD_HD int jpeg_check_record(const BasdJpegRecord& r, long src_bytes, long out_bytes, long ws_bytes, long ws_reserved) {
-    if (!jpeg_out_ok(r, out_bytes)) return BASD_JPEG_BAD_RECORD;
-    if (r.src_len < 0 || r.src_len > 0x7fffffff - 16 || r.src_offset < 0 || r.src_offset > src_bytes || r.src_len > src_bytes - r.src_offset)
-        return BASD_JPEG_BAD_RECORD;
-    if (r.kind == BASD_JPEG_KIND_RAW) return (long)r.src_len == 3L * r.width * r.height ? 0 : BASD_JPEG_BAD_RECORD;
-    if (r.kind != BASD_JPEG_KIND_STREAM) return BASD_JPEG_BAD_RECORD;
-    if (r.ncomp != 1 && r.ncomp != 3) return BASD_JPEG_BAD_RECORD;
-    if (r.ncomp == 3 && !((r.hs == 1 && r.vs == 1) || (r.hs == 2 && r.vs == 1) || (r.hs == 2 && r.vs == 2)))
-        return BASD_JPEG_BAD_RECORD;
+// The output range and the source range of a record (every kind has both).
+BASD_HD bool jpeg_ranges_ok(const BasdJpegRecord& r, long src_bytes, long out_bytes) {
+    if (!jpeg_out_ok(r, out_bytes)) return false;
+    return !(r.src_len < 0 || r.src_len > 0x7fffffff - 16 || r.src_offset < 0 || r.src_offset > src_bytes ||
+             r.src_len > src_bytes - r.src_offset);
+}
+
+// The frame of a stream, baseline or progressive: components, sampling, its places in the workspace, its DQT tables.
+BASD_HD bool jpeg_frame_ok(const BasdJpegRecord& r, long ws_bytes, long ws_reserved) {
+    if (r.ncomp != 1 && r.ncomp != 3) return false;
+    if (r.ncomp == 3 && !((r.hs == 1 && r.vs == 1) || (r.hs == 2 && r.vs == 1) || (r.hs == 2 && r.vs == 2))) return false;
     const JpegGeometry g = jpeg_geometry(r);
     if (r.coef_offset < ws_reserved || (r.coef_offset & 15) || r.coef_offset > ws_bytes ||
         g.blocks * 128 > ws_bytes - r.coef_offset)
-        return BASD_JPEG_BAD_RECORD;
+        return false;
     if (r.plane_offset < ws_reserved || (r.plane_offset & 7) || r.plane_offset > ws_bytes ||
         g.blocks * 64 > ws_bytes - r.plane_offset)
-        return BASD_JPEG_BAD_RECORD;
+        return false;
+    for (int c = 0; c < r.ncomp; ++c)
+        if (r.quant[c] < 0 || r.quant[c] > r.src_len - 64) return false;
+    return true;
+}
+
+// Every field of a record against the three buffers: 0, or BASD_JPEG_BAD_RECORD.  (A progressive record is one here:
+// only basd_jpeg_decode_progressive takes it, through jpeg_check_progressive.)
+BASD_HD int jpeg_check_record(const BasdJpegRecord& r, long src_bytes, long out_bytes, long ws_bytes, long ws_reserved) {
+    if (!jpeg_ranges_ok(r, src_bytes, out_bytes)) return BASD_JPEG_BAD_RECORD;
+    if (r.kind == BASD_JPEG_KIND_RAW) return (long)r.src_len == 3L * r.width * r.height ? 0 : BASD_JPEG_BAD_RECORD;
+    if (r.kind != BASD_JPEG_KIND_STREAM) return BASD_JPEG_BAD_RECORD;
+    if (!jpeg_frame_ok(r, ws_bytes, ws_reserved)) return BASD_JPEG_BAD_RECORD;
     if (r.restart < 0 || r.n_seg < 1) return BASD_JPEG_BAD_RECORD;
     if (r.seg_offset < 0 || (r.seg_offset & 3) || r.seg_offset > src_bytes || 4L * r.n_seg > src_bytes - r.seg_offset)
         return BASD_JPEG_BAD_RECORD;
-    for (int c = 0; c < r.ncomp; ++c) {
-        if (r.quant[c] < 0 || r.quant[c] > r.src_len - 64) return BASD_JPEG_BAD_RECORD;
+    for (int c = 0; c < r.ncomp; ++c)
         if (r.dc[c] < 0 || r.dc[c] > r.src_len - 16 || r.ac[c] < 0 || r.ac[c] > r.src_len - 16)
             return BASD_JPEG_BAD_RECORD;
-    }
     return 0;
 }
 
@@ -464,6 +475,215 @@ BASD_HD JpegSubPass jpeg_sub_pass(const JpegSubSegment& g, JpegSubState in, int 
     }
     if (kWrite) out.error = bad;
     return out;
+}
+
+// ---- progressive streams (basd_jpeg_decode_progressive) -----------------------------------------------------------------
+// The record of a progressive stream against the buffers, its scan table included (not yet the rows: jpeg_check_scan):
+// 0, or BASD_JPEG_BAD_RECORD.
+BASD_HD int jpeg_check_progressive(const BasdJpegRecord& r, long src_bytes, long out_bytes, long ws_bytes, long ws_reserved,
+                                   int max_scans) {
+    if (r.kind != BASD_JPEG_KIND_PROGRESSIVE || !jpeg_ranges_ok(r, src_bytes, out_bytes) ||
+        !jpeg_frame_ok(r, ws_bytes, ws_reserved))
+        return BASD_JPEG_BAD_RECORD;
+    if (r.n_scans < 1 || r.n_scans > BASD_JPEG_MAX_SCANS || r.n_scans > max_scans) return BASD_JPEG_BAD_RECORD;
+    const long at = r.src_offset + (long)r.scan_offset;
+    if (r.scan_offset < 0 || (at & 7) || at > src_bytes || (long)sizeof(BasdJpegScan) * r.n_scans > src_bytes - at)
+        return BASD_JPEG_BAD_RECORD;
+    return 0;
+}
+
+BASD_HD int jpeg_pick(const int v[3], int c);            // (below)
+
+// Row `s` of a scan table whose record has passed jpeg_check_progressive: is every field inside its bounds?
+BASD_HD bool jpeg_check_scan(const BasdJpegRecord& r, const BasdJpegScan& s, long src_bytes, int max_segments) {
+    if (s.n_seg < 1 || s.n_seg > max_segments || s.restart < 0) return false;
+    const long at = r.src_offset + (long)s.seg_offset;
+    if (s.seg_offset < 0 || (at & 3) || at > src_bytes || 4L * s.n_seg > src_bytes - at) return false;
+    if (s.data_end < 0 || s.data_end > r.src_len) return false;
+    if (s.comp < 0 || s.comp >= r.ncomp || !(s.ncomp == 1 || (s.ncomp == r.ncomp && s.comp == 0))) return false;
+    if (s.al < 0 || s.al > 13 || s.ah < 0 || s.ah > 14 || s.level < 0 || s.level >= r.n_scans) return false;
+    if (s.ss == 0) {
+        if (s.se != 0) return false;
+        if (s.ah == 0)
+            for (int c = 0; c < r.ncomp; ++c)
+                if ((s.ncomp > 1 || c == s.comp) && (jpeg_pick(s.dc, c) < 0 || jpeg_pick(s.dc, c) > r.src_len - 16)) return false;
+    } else {
+        if (s.ss < 1 || s.se < s.ss || s.se > 63 || s.ncomp != 1) return false;
+        if (s.ac < 0 || s.ac > r.src_len - 16) return false;
+    }
+    return true;
+}
+
+// The scan units of a scan (MCUs of an interleaved scan, the component's own blocks otherwise) and, for a one-component
+// scan, the blocks in a row of its grid.
+BASD_HD long jpeg_scan_units(const BasdJpegRecord& r, const JpegGeometry& g, const BasdJpegScan& s, int& row) {
+    if (s.ncomp > 1) {
+        row = g.mcux;
+        return g.mcus;
+    }
+    const int cw = s.comp == 0 ? r.width : g.cwr, ch = s.comp == 0 ? r.height : g.chr;
+    row = (cw + 7) / 8;
+    return (long)row * ((ch + 7) / 8);
+}
+
+BASD_HD bool jpeg_scan_segments_ok(const BasdJpegScan& s, long units) {
+    return (long)s.n_seg == (s.restart > 0 ? (units + s.restart - 1) / s.restart : 1);
+}
+
+// Block (bx, by) of component `comp`'s own grid: its index in the interleaved order of the coefficient area.
+BASD_HD long jpeg_component_block(const BasdJpegRecord& r, const JpegGeometry& g, int comp, int bx, int by) {
+    if (r.ncomp == 1) return (long)by * g.mcux + bx;
+    if (comp) return ((long)by * g.mcux + bx) * g.bpm + (g.bpm - 3 + comp);
+    return ((long)(by / r.vs) * g.mcux + bx / r.hs) * g.bpm + (by % r.vs) * r.hs + bx % r.hs;
+}
+
+BASD_HD int jpeg_bit(JpegBits& b) {                     // one bit; b.nbits < 0 behind it: the data had none
+    if (b.nbits <= 0) jpeg_bits_fill(b);
+    const int v = (int)(b.acc >> 63);
+    jpeg_bits_skip(b, 1);
+    return v;
+}
+
+// The four kinds of scan on one block (64 int16 in zigzag order, in the coefficient area): 0 or a BASD_JPEG_BAD_* code.
+BASD_HD int jpeg_prog_dc_first(JpegBits& b, const JpegHuff* dc, int& pred, int al, short* block) {
+    jpeg_bits_fill(b);
+    const int s = jpeg_symbol(b, dc);
+    if (b.nbits < 0) return BASD_JPEG_TRUNCATED;
+    if (s < 0) return -s;
+    if (s > 15) return BASD_JPEG_BAD_VALUE;
+    if (s) pred += jpeg_extend(b, s);
+    if (b.nbits < 0) return BASD_JPEG_TRUNCATED;
+    if (pred < -32768 || pred > 32767) return BASD_JPEG_BAD_VALUE;
+    block[0] = (short)(unsigned short)(pred * (1 << al));             // wraps to 16 bits
+    return 0;
+}
+
+BASD_HD int jpeg_prog_dc_refine(JpegBits& b, int al, short* block) {
+    if (jpeg_bit(b)) block[0] = (short)(block[0] | (1 << al));
+    return b.nbits < 0 ? BASD_JPEG_TRUNCATED : 0;
+}
+
+BASD_HD int jpeg_prog_ac_first(JpegBits& b, const JpegHuff* ac, int ss, int se, int al, int& eobrun, short* block) {
+    if (eobrun > 0) {
+        --eobrun;
+        return 0;
+    }
+    for (int k = ss; k <= se;) {
+        jpeg_bits_fill(b);
+        const int rs = jpeg_symbol(b, ac);
+        if (b.nbits < 0) return BASD_JPEG_TRUNCATED;
+        if (rs < 0) return -rs;
+        const int r = rs >> 4, s = rs & 15;
+        if (s) {
+            k += r;
+            if (k > se) return BASD_JPEG_BAD_INDEX;
+            block[k] = (short)(unsigned short)(jpeg_extend(b, s) * (1 << al));
+            ++k;
+        } else if (r == 15) {
+            k += 16;
+        } else {
+            eobrun = (1 << r) - 1;
+            if (r) {
+                eobrun += (int)jpeg_bits_peek(b, r);
+                jpeg_bits_skip(b, r);
+            }
+            break;
+        }
+    }
+    return b.nbits < 0 ? BASD_JPEG_TRUNCATED : 0;
+}
+
+BASD_HD void jpeg_prog_correct(JpegBits& b, short* at, int p1) {
+    const int v = *at;
+    if (jpeg_bit(b) && !(v & p1)) *at = (short)(unsigned short)(v + (v >= 0 ? p1 : -p1));
+}
+
+BASD_HD int jpeg_prog_ac_refine(JpegBits& b, const JpegHuff* ac, int ss, int se, int al, int& eobrun, short* block) {
+    const int p1 = 1 << al;
+    int k = ss;
+    if (eobrun == 0) {
+        while (k <= se) {
+            jpeg_bits_fill(b);
+            const int rs = jpeg_symbol(b, ac);
+            if (b.nbits < 0) return BASD_JPEG_TRUNCATED;
+            if (rs < 0) return -rs;
+            int r = rs >> 4, value = 0;
+            if (rs & 15) {
+                if ((rs & 15) != 1) return BASD_JPEG_BAD_CODE;
+                value = jpeg_bit(b) ? p1 : -p1;
+            } else if (r != 15) {
+                eobrun = 1 << r;
+                if (r) {
+                    eobrun += (int)jpeg_bits_peek(b, r);
+                    jpeg_bits_skip(b, r);
+                }
+                break;
+            }
+            for (; k <= se; ++k) {                                     // the walk
+                if (block[k]) jpeg_prog_correct(b, block + k, p1);
+                else if (--r < 0) break;
+            }
+            if (b.nbits < 0) return BASD_JPEG_TRUNCATED;
+            if (value) {
+                if (k > se) return BASD_JPEG_BAD_INDEX;
+                block[k] = (short)value;
+            }
+            ++k;
+        }
+    }
+    if (eobrun > 0) {
+        for (; k <= se; ++k)
+            if (block[k]) jpeg_prog_correct(b, block + k, p1);
+        --eobrun;
+    }
+    return b.nbits < 0 ? BASD_JPEG_TRUNCATED : 0;
+}
+
+// Segment `seg` of scan `s` (its row has passed jpeg_check_scan and its segment count jpeg_scan_segments_ok), in place
+// in the coefficient area `coef`; `tables`: DC first scans, the table of FRAME component c at tables[c]; AC scans, the
+// table at tables[0].  0 or a BASD_JPEG_BAD_* code.
+BASD_HD int jpeg_scan_segment(const BasdJpegRecord& r, const JpegGeometry& g, const BasdJpegScan& s,
+                              const unsigned char* src, int seg, const JpegHuff* tables, short* coef) {
+    const unsigned char* stream = src + r.src_offset;
+    const unsigned char* starts = stream + s.seg_offset;
+    int start, end = s.data_end + 2;
+    __builtin_memcpy(&start, __builtin_assume_aligned(starts + 4L * seg, 4), 4);
+    if (seg + 1 < s.n_seg) __builtin_memcpy(&end, __builtin_assume_aligned(starts + 4L * (seg + 1), 4), 4);
+    if (end < 2) return BASD_JPEG_BAD_RESTART;
+    end -= 2;
+    if (start < 2 || start > r.src_len || end < start || end > r.src_len) return BASD_JPEG_BAD_RESTART;
+    if (seg > 0 && (stream[start - 2] != 0xFF || stream[start - 1] != 0xD0 + ((seg - 1) & 7)))
+        return BASD_JPEG_BAD_RESTART;
+    int row;
+    const long units = jpeg_scan_units(r, g, s, row);
+    const long per = s.restart > 0 ? s.restart : units;
+    const long first = (long)seg * per;
+    const long last = first + per < units ? first + per : units;
+    JpegBits b;
+    jpeg_bits_open(b, src, r.src_offset + start, end - start);
+    const int luma = r.ncomp == 1 ? 1 : g.bpm - 2;
+    const int per_unit = s.ncomp > 1 ? g.bpm : 1;
+    int pred0 = 0, pred1 = 0, pred2 = 0, eobrun = 0;
+    for (long u = first; u < last; ++u) {
+        for (int j = 0; j < per_unit; ++j) {
+            int c = s.comp;
+            long at = u * g.bpm + j;
+            if (s.ncomp > 1) c = j < luma ? 0 : j == luma ? 1 : 2;
+            else at = jpeg_component_block(r, g, c, (int)(u % row), (int)(u / row));
+            short* block = coef + at * 64;
+            int bad;
+            if (s.ss == 0 && s.ah == 0)
+                bad = jpeg_prog_dc_first(b, tables + c, c == 0 ? pred0 : c == 1 ? pred1 : pred2, s.al, block);
+            else if (s.ss == 0)
+                bad = jpeg_prog_dc_refine(b, s.al, block);
+            else if (s.ah == 0)
+                bad = jpeg_prog_ac_first(b, tables, s.ss, s.se, s.al, eobrun, block);
+            else
+                bad = jpeg_prog_ac_refine(b, tables, s.ss, s.se, s.al, eobrun, block);
+            if (bad) return bad;
+        }
+    }
+    return 0;
 }
 
 // ---- IDCT ---------------------------------------------------------------------------------------------------------
