@@ -931,65 +931,87 @@ typedef struct BasdTaugRecord {
 int basd_trivial_augment(const unsigned char* src, unsigned char* dst, int B, int C, int H, int W,
                          const BasdTaugRecord* table, int* status, hipStream_t stream);
 
-/* ---- Pillow-exact crops and bilinear resizes of ragged uint8 images in one launch ------------------------- */
+/* ---- Pillow-exact crops and resizes (bilinear, bicubic, box) of ragged uint8 images in one launch ------------ */
 
 /* The horizontal pass of a band of output rows is staged in LDS as bytes: source rows x columns x C of one stage stay
  * inside this budget; a band whose rows need more is cut into shorter ones, a wide or strongly reduced image into
  * column chunks. */
 #define BASD_RESIZE_STAGE_BYTES 40960
-/* The largest reduction per axis: window size <= BASD_RESIZE_MAX_RATIO * resized size (at most 65 taps per pixel). */
+/* The largest reduction per axis: window size <= BASD_RESIZE_MAX_RATIO * resized size (at most 65 taps per pixel).
+ * A filter of wider support admits less: ceil(S_f * in / out) <= BASD_RESIZE_MAX_RATIO, see the limits below. */
 #define BASD_RESIZE_MAX_RATIO 32
 /* Source and resized sides are at most this. */
 #define BASD_RESIZE_MAX_SIDE 1048576
 
 #define BASD_RESIZE_BAD_GEOMETRY 1   /* status bit 0: a window, rectangle, size or offset outside its bounds */
-#define BASD_RESIZE_BAD_RATIO 2      /* status bit 1: a reduction above BASD_RESIZE_MAX_RATIO */
+#define BASD_RESIZE_BAD_RATIO 2      /* status bit 1: a reduction above the filter's limit */
+#define BASD_RESIZE_BAD_FILTER 4     /* status bit 2: a filter that is none of BASD_RESIZE_FILTER_* */
 
-/* One row of the device table, one per OUTPUT image (64 bytes).  Two records may name one source. */
+/* The resampling filter of a record: Pillow's Image.BILINEAR, Image.BICUBIC, Image.BOX. */
+#define BASD_RESIZE_FILTER_BILINEAR 0
+#define BASD_RESIZE_FILTER_BICUBIC 1
+#define BASD_RESIZE_FILTER_BOX 2
+
+/* One row of the device table, one per OUTPUT image (64 bytes).  Two records may name one source, with one filter or
+ * with two. */
 typedef struct BasdResizeRecord {
     long long src_offset;         /* byte offset of the source image in the packed buffer */
     int src_h, src_w;             /* the source: interleaved HWC, row pitch src_w * C bytes */
     int win_x, win_y, win_w, win_h;   /* the crop window inside the source */
     int res_w, res_h;             /* the size the window is resized to */
     int out_x, out_y;             /* top-left corner of the OH x OW output rectangle inside the resized image */
-    int pad[4];
+    int filter;                   /* BASD_RESIZE_FILTER_* (byte offset 48; 0, what a zeroed record holds: bilinear) */
+    int pad[3];
 } BasdResizeRecord;
 
 /* replaces: `v2.RandomResizedCrop(image_size)` of the training transform and `v2.Resize(round(image_size / crop_ratio)),
  *           v2.CenterCrop(image_size)` of the clean and the validation transform  src/data/datasets.py:80-94,137-149,
- *           which the reference runs per image in Pillow inside its loader's workers (and twice per training image).
+ *           which the reference runs per image in Pillow inside its loader's workers (and twice per training image),
+ *           with their `interpolation` argument (BILINEAR, the reference's default; BICUBIC; BOX) chosen per record.
  * src: one packed uint8 buffer of src_bytes bytes holding the decoded images (HWC, `np.asarray(img.convert("RGB"))`)
  * back to back at any byte address; dst: dense (n, C, OH, OW) uint8, planar, not overlapping src (checked);
  * table: n records on the device; status: one int on the device, OR-ed into (BASD_RESIZE_BAD_*).
  *   dst[i] = resize(window_i)[out_y : out_y + OH, out_x : out_x + OW]
  * This text is the specification; the kernel equals it byte for byte, and it equals Pillow 12's
- * `Image.crop((win_x, win_y, win_x + win_w, win_y + win_h)).resize((res_w, res_h), Image.BILINEAR)` byte for byte
+ * `Image.crop((win_x, win_y, win_x + win_w, win_y + win_h)).resize((res_w, res_h), F)` byte for byte for F =
+ * Image.BILINEAR, Image.BICUBIC, Image.BOX
  * (8-bit ImagingResample on the window as an image of its own: taps clamp at the window, not at the source).
  *
  * Per axis, with `in` the window size, `out` the resized size: scale = double(in) / out, fs = max(scale, 1.0),
- * support = fs, inv = 1.0 / fs.  For output index xx: center = (xx + 0.5) * scale,
+ * support = S_f * fs with S_f = 1.0 (bilinear), 2.0 (bicubic), 0.5 (box), inv = 1.0 / fs.  For output index xx:
+ * center = (xx + 0.5) * scale,
  *   xmin = max(int(center - support + 0.5), 0),  xmax = min(int(center + support + 0.5), in)     (int: towards zero),
- * for x = 0 .. xmax - xmin - 1 in increasing x: a = |(x + xmin - center + 0.5) * inv|, w_x = a < 1 ? 1 - a : 0;
- * ww = the running sum of the w_x; if ww != 0: w_x = w_x / ww;  k_x = int(0.5 + w_x * 2^22).  All of it fp64, from
- * left to right, every operation rounded on its own (no fused multiply-add).
- * A pass works on bytes: acc = 2^21 + sum_x k_x * p[xmin + x] in int32, result = clamp(acc >> 22, 0, 255).  The
- * horizontal pass runs first and is rounded to uint8; the vertical pass runs on those bytes.  A pass with in == out is
- * the identity under these formulas (it is not special-cased).
+ * for x = 0 .. xmax - xmin - 1 in increasing x: t = (x + xmin - center + 0.5) * inv, w_x = f(t) with
+ *   bilinear: a = |t|, w_x = a < 1 ? 1 - a : 0;
+ *   box:      -0.5 < t <= 0.5 ? 1 : 0  (of t itself, not of |t|: the asymmetry is Pillow's);
+ *   bicubic:  a = -0.5, t = |t|:  t < 1: ((a + 2) * t - (a + 3)) * t * t + 1;  t < 2: (((t - 5) * t + 8) * t - 4) * a;
+ *             otherwise 0  (evaluated in exactly this order);
+ * ww = the running sum of the w_x; if ww != 0: w_x = w_x / ww;  k_x = int(0.5 + w_x * 2^22) for w_x >= 0 and
+ * k_x = int(-0.5 + w_x * 2^22) for w_x < 0.  All of it fp64, from left to right, every operation rounded on its own
+ * (no fused multiply-add).
+ * A pass works on bytes: acc = 2^21 + sum_x k_x * p[xmin + x] in int32, result = clamp(acc >> 22, 0, 255) with an
+ * arithmetic shift (bicubic's negative lobes take acc below 0 and above 255 << 22; sum |k_x| stays near 1.25 * 2^22,
+ * so acc stays inside int32).  The horizontal pass runs first and is rounded to uint8; the vertical pass runs on those
+ * bytes.  A pass with in == out is the identity under these formulas for all three filters (it is not special-cased).
  *
  * Limits, checked per record by the kernel (and by basd_amd.resize on the host): 1 <= src_h, src_w, res_h, res_w <=
  * BASD_RESIZE_MAX_SIDE; 0 <= src_offset and src_offset + src_h * src_w * C <= src_bytes; the window is not empty and
  * lies inside the source; the output rectangle lies inside the resized image (no padding: a centre crop of an image
- * smaller than the crop is refused); in <= BASD_RESIZE_MAX_RATIO * out on both axes.  A record that violates one gets
- * an all-zero output image and its bit in the status word; nothing of it is read.
+ * smaller than the crop is refused); filter is one of BASD_RESIZE_FILTER_*; on both axes in <= BASD_RESIZE_MAX_RATIO *
+ * out and ceil(S_f * max(in / out, 1)) <= BASD_RESIZE_MAX_RATIO, so that a pixel has at most 65 taps: reductions up to
+ * 32 for bilinear and box, up to 16 for bicubic (a larger one is refused with BASD_RESIZE_BAD_RATIO, not resampled
+ * another way).  A record that violates one gets an all-zero output image and its bit in the status word; nothing of
+ * it is read.
  *
  * Grid: (bands of band_rows output rows) x records.  A workgroup makes the horizontal coefficients of its columns and
  * the vertical ones of its rows once, runs the horizontal pass for the source rows its rows' taps need into LDS, and
- * the vertical pass out of LDS, four output bytes of a row per lane and store.  band_rows: 0 = the entry point chooses
- * (32, halved down to 4 while the grid would have fewer than 1024 workgroups); 1..32 = a test / tuning hook (the
+ * the vertical pass out of LDS, four output bytes of a row per lane and store.  The filter is a field of the record and
+ * so uniform over a workgroup: records of different filters share a table and a launch.  band_rows: 0 = the entry point
+ * chooses (32, halved down to 4 while the grid would have fewer than 1024 workgroups); 1..32 = a test / tuning hook (the
  * result does not depend on it).  ONE launch on `stream`; no allocation, no memset, no workspace, no wait for the device.
  * n == 0 launches nothing; C outside {1, 3}, OH or OW outside 1..BASD_RESIZE_MAX_SIDE, C*OH*OW >= 2^30, src_bytes < 0,
  * band_rows outside 0..32, more than 2^31 - 1 workgroups or overlapping buffers return BASD_EINVAL before anything is
- * launched. */
+ * launched.  The per-axis code (taps, tap count, record check) is csrc/resize_core.h, shared with a host program. */
 int basd_resize_crop(const unsigned char* src, long src_bytes, unsigned char* dst, int n, int C, int OH, int OW,
                      const BasdResizeRecord* table, int* status, int band_rows, hipStream_t stream);
 

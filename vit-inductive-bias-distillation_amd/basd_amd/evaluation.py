@@ -123,7 +123,8 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
     whatever ``image_stats`` and ``input_dtype`` say.
     ``resize_crop``: a ``basd_amd.resize.ResizeCrop``; with it a batch may carry ``images`` (a ``RaggedBatch`` of decoded
     images, ``collate_fn=collate_ragged``) instead of ``pixel_values``: one launch makes the clean view (``Resize ->
-    CenterCrop``), which then takes the uint8 path above, so ``image_stats`` is needed (``ValueError`` otherwise).
+    CenterCrop``, resampled with the instance's ``interpolation["clean"]``: validation is the clean geometry), which
+    then takes the uint8 path above, so ``image_stats`` is needed (``ValueError`` otherwise).
     ``jpeg_decode``: a ``basd_amd.jpeg.JpegDecoder`` (it needs ``resize_crop``); with it ``images`` may be a ``JpegBatch``
     of the files' bytes (``collate_fn=collate_jpeg``), decoded on the device ahead of the resize launch (progressive files
     too where the batch was packed with ``collate_jpeg(..., progressive=True)``: the choice is the collate function's).

@@ -9,8 +9,12 @@ views of every image come out of one launch as the dense uint8 NCHW batches ``Tr
 sizes into a table of fixed-size records (``BasdResizeRecord`` of ``include/basd_hip.h``, which also holds the
 specification of the resize), sends it with one non-blocking copy and launches once.
 
-The resize is Pillow's 8-bit bilinear ``ImagingResample`` of the cropped window, byte for byte: the specification is
-held to Pillow and the kernel to the specification in ``tests/test_resize_crop.py``.  ``torchvision`` is not installed
+The resize is Pillow's 8-bit ``ImagingResample`` of the cropped window, byte for byte, with the filter ``interpolation``
+names -- ``"bilinear"`` (the default, the reference's), ``"bicubic"`` or ``"box"``, one for all or one per view: the
+specification is held to Pillow and the kernel to the specification in ``tests/test_resize_crop.py`` and
+``tests/test_resize_filters.py``.  This is what torchvision's PIL backend does (``Resize(interpolation=BICUBIC)`` on a
+PIL image is ``img.resize(size, Image.BICUBIC)`` by its documentation), which is the backend the reference's loader
+uses ahead of ``ToImage()``; torchvision's tensor backend resamples in floating point and is not matched.  ``torchvision`` is not installed
 where this was written: the draw order and RNG consumption of ``RandomResizedCrop.get_params``, the ``int(...)`` of
 ``Resize``'s long side and the ``round`` of ``CenterCrop`` are restated from the package's documentation and are NOT
 verified against it.  There is no CPU fallback.
@@ -18,7 +22,7 @@ verified against it.  There is no CPU fallback.
 from __future__ import annotations
 
 import math
-from typing import NamedTuple, Optional, Sequence
+from typing import NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -27,18 +31,55 @@ from . import _lib
 from ._launch import RecordTable, batch_columns, lives_on, raw_stream, require_gpu
 
 __all__ = ["RaggedBatch", "pack_images", "collate_ragged", "eval_window", "CropParams", "draw_crop_params",
-           "make_records", "RECORD_DTYPE", "ResizeCrop", "resize_reference", "VIEWS", "MAX_RATIO", "MAX_SIDE"]
+           "make_records", "RECORD_DTYPE", "ResizeCrop", "resize_reference", "VIEWS", "MAX_RATIO", "MAX_SIDE",
+           "INTERPOLATIONS", "max_reduction"]
 
 VIEWS = ("clean", "augmented")
 MAX_RATIO = 32                      # BASD_RESIZE_MAX_RATIO
 MAX_SIDE = 1 << 20                  # BASD_RESIZE_MAX_SIDE
-BAD_GEOMETRY, BAD_RATIO = 1, 2      # BASD_RESIZE_BAD_*
+BAD_GEOMETRY, BAD_RATIO, BAD_FILTER = 1, 2, 4      # BASD_RESIZE_BAD_*
+INTERPOLATIONS = ("bilinear", "bicubic", "box")    # BASD_RESIZE_FILTER_*: a name's index is its value in a record
+_SUPPORT = {"bilinear": 1.0, "bicubic": 2.0, "box": 0.5}
+_EXCLUDED = {
+    "hamming": "its weights need cos, whose last bit differs between math libraries, so the coefficients cannot be "
+               "promised to be Pillow's byte for byte",
+    "lanczos": "its weights need sin, whose last bit differs between math libraries, so the coefficients cannot be "
+               "promised to be Pillow's byte for byte",
+    "nearest": "Pillow does not resample it with ImagingResample but with a different code path (an affine transform), "
+               "which is not restated here",
+}
 
 # BasdResizeRecord: 64 bytes
 RECORD_DTYPE = np.dtype([("src_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"), ("win_x", "<i4"), ("win_y", "<i4"),
                          ("win_w", "<i4"), ("win_h", "<i4"), ("res_w", "<i4"), ("res_h", "<i4"), ("out_x", "<i4"),
-                         ("out_y", "<i4"), ("pad", "<i4", (4,))])
-assert RECORD_DTYPE.itemsize == 64
+                         ("out_y", "<i4"), ("filter", "<i4"), ("pad", "<i4", (3,))])
+assert RECORD_DTYPE.itemsize == 64 and RECORD_DTYPE.fields["filter"][1] == 48
+
+
+def _filter_name(name) -> str:
+    if isinstance(name, str) and name.lower() in INTERPOLATIONS:
+        return name.lower()
+    if isinstance(name, str) and name.lower() in _EXCLUDED:
+        raise ValueError(f"interpolation {name!r} is not offered: {_EXCLUDED[name.lower()]}; choose one of "
+                         f"{INTERPOLATIONS}")
+    raise ValueError(f"interpolation must be one of {INTERPOLATIONS} (got {name!r})")
+
+
+def _check_interpolation(interpolation) -> dict:
+    """``{view: filter name}`` for both views of a name or of a dict per view (a view it leaves out is bilinear)."""
+    if isinstance(interpolation, dict):
+        unknown = [v for v in interpolation if v not in VIEWS]
+        if unknown:
+            raise ValueError(f"interpolation names the views {unknown}; the views are {VIEWS}")
+        return {view: _filter_name(interpolation.get(view, "bilinear")) for view in VIEWS}
+    name = _filter_name(interpolation)
+    return dict.fromkeys(VIEWS, name)
+
+
+def max_reduction(filter: str = "bilinear") -> int:
+    """The largest ``window / resized`` per axis the launch takes with ``filter``: ``ceil(support * ratio) <= 32`` and
+    never above ``MAX_RATIO``, so 32 for bilinear and box, 16 for bicubic."""
+    return min(MAX_RATIO, int(MAX_RATIO / _SUPPORT[_filter_name(filter)]))
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -262,14 +303,18 @@ def _check_views(views) -> tuple:
 
 
 def make_records(sizes, image_size: int, crop_ratio: float, crop_params: Optional[CropParams] = None, *,
-                 views=VIEWS, offsets=None, channels: int = 3, out: Optional[np.ndarray] = None) -> np.ndarray:
+                 views=VIEWS, offsets=None, channels: int = 3, out: Optional[np.ndarray] = None,
+                 interpolation: Union[str, dict] = "bilinear") -> np.ndarray:
     """The record table of a ragged batch: ``len(views) * B`` entries of ``RECORD_DTYPE``, view-major (the records of
     ``views[0]`` for all images, then those of ``views[1]``).  ``"clean"``: the whole image as the window, resized as
     ``eval_window`` says, the centre crop as the output rectangle.  ``"augmented"``: the window of ``crop_params``
     resized to ``image_size`` x ``image_size``.  ``offsets``: the images' byte offsets (default: back to back with
-    ``channels`` bytes per pixel).  Every limit of ``include/basd_hip.h`` is checked here; a violation raises
-    ``ValueError``."""
+    ``channels`` bytes per pixel).  ``interpolation``: one of ``INTERPOLATIONS`` for every record, or a dict per view such
+    as ``{"clean": "bicubic", "augmented": "bilinear"}``; it fills the records' ``filter``.  Every limit of
+    ``include/basd_hip.h`` is checked here, the reduction against the limit of the view's filter (``max_reduction``);
+    a violation raises ``ValueError``."""
     views = _check_views(views)
+    filters = _check_interpolation(interpolation)
     sizes = _sizes_of(sizes)
     S, B = int(image_size), sizes.shape[0]
     if S < 1:
@@ -293,12 +338,15 @@ def make_records(sizes, image_size: int, crop_ratio: float, crop_params: Optiona
     for v, view in enumerate(views):
         part = rec[v * B:(v + 1) * B]
         part["src_offset"], part["src_h"], part["src_w"] = offsets, H, W
+        name = filters[view]
+        part["filter"] = INTERPOLATIONS.index(name)
+        most = max_reduction(name)
         if view == "clean":
             geo = [eval_window(H[b], W[b], S, crop_ratio) for b in range(B)]
             for b, (res_h, res_w, _, _) in enumerate(geo):
-                if H[b] > MAX_RATIO * res_h or W[b] > MAX_RATIO * res_w or max(res_h, res_w) > MAX_SIDE:
+                if H[b] > most * res_h or W[b] > most * res_w or max(res_h, res_w) > MAX_SIDE:
                     raise ValueError(f"image {b} ({H[b]} x {W[b]}) resized to {res_h} x {res_w} is outside the limits "
-                                     f"(a reduction of at most {MAX_RATIO} per axis, sides up to {MAX_SIDE})")
+                                     f"(a {name} reduction of at most {most} per axis, sides up to {MAX_SIDE})")
             if B:
                 part["win_w"], part["win_h"] = W, H
                 part["res_h"], part["res_w"] = [g[0] for g in geo], [g[1] for g in geo]
@@ -312,9 +360,9 @@ def make_records(sizes, image_size: int, crop_ratio: float, crop_params: Optiona
                         and left[b] + ww[b] <= W[b]):
                     raise ValueError(f"the crop window of image {b} (top {top[b]}, left {left[b]}, {hh[b]} x {ww[b]}) "
                                      f"does not lie inside its {H[b]} x {W[b]} image")
-                if hh[b] > MAX_RATIO * S or ww[b] > MAX_RATIO * S:
-                    raise ValueError(f"the crop window of image {b} ({hh[b]} x {ww[b]}) is more than {MAX_RATIO} times "
-                                     f"the image size {S}")
+                if hh[b] > most * S or ww[b] > most * S:
+                    raise ValueError(f"the crop window of image {b} ({hh[b]} x {ww[b]}) is more than {most} times "
+                                     f"the image size {S} (the limit of a {name} reduction)")
             if B:
                 part["win_x"], part["win_y"], part["win_w"], part["win_h"] = left, top, ww, hh
                 part["res_w"], part["res_h"] = S, S
@@ -325,7 +373,11 @@ def make_records(sizes, image_size: int, crop_ratio: float, crop_params: Optiona
 # the launch
 # ----------------------------------------------------------------------------------------------------------------
 class ResizeCrop:
-    """``ResizeCrop(image_size, crop_ratio, device=...)``.
+    """``ResizeCrop(image_size, crop_ratio, device=..., interpolation="bilinear")``.
+
+    ``interpolation``: one of ``INTERPOLATIONS``, or a dict per view (``{"clean": "bicubic", "augmented": "bilinear"}``:
+    the clean view the way a timm teacher was trained, the augmented one as the reference makes it); ``.interpolation``
+    is the dict of both views.  Records of different filters share the table and the launch.
 
     ``rc(ragged, crop_params=None, *, views=("clean", "augmented")) -> {view: uint8 (B, C, S, S)}``: ``ragged`` a
     ``RaggedBatch`` whose data lives on ``device``; ``crop_params=None`` draws with ``draw_crop_params`` (global CPU
@@ -334,13 +386,15 @@ class ResizeCrop:
     largest batch seen); then exactly one launch on the current stream, no wait for the device.  ``status()`` reads
     the kernel's status word back (0: clean; it waits for the device)."""
 
-    def __init__(self, image_size: int, crop_ratio: float, *, device) -> None:
+    def __init__(self, image_size: int, crop_ratio: float, *, device,
+                 interpolation: Union[str, dict] = "bilinear") -> None:
         self.image_size = int(image_size)
         self.crop_ratio = float(crop_ratio)
         if self.image_size < 1 or self.image_size > MAX_SIDE:
             raise ValueError(f"image_size must lie in [1, {MAX_SIDE}] (got {image_size})")
         if not self.crop_ratio > 0.0:
             raise ValueError(f"crop_ratio must be positive (got {crop_ratio})")
+        self.interpolation = _check_interpolation(interpolation)
         self.device = torch.device(device)
         self._records = RecordTable(RECORD_DTYPE)
 
@@ -360,7 +414,8 @@ class ResizeCrop:
         if crop_params is None and "augmented" in views:
             crop_params = draw_crop_params(ragged.sizes)
         offsets = ragged.offsets
-        checked = make_records(ragged.sizes, S, self.crop_ratio, crop_params, views=views, offsets=offsets)
+        checked = make_records(ragged.sizes, S, self.crop_ratio, crop_params, views=views, offsets=offsets,
+                               interpolation=self.interpolation)
         require_gpu(ragged.data, f"the {B} images")
         n = len(views) * B
         out = torch.empty((n, C, S, S), dtype=torch.uint8, device=ragged.device)
@@ -376,40 +431,62 @@ class ResizeCrop:
 # ----------------------------------------------------------------------------------------------------------------
 # the specification in numpy (tests and the goldens script; the product path does not use it)
 # ----------------------------------------------------------------------------------------------------------------
-def _reference_taps(size_in: int, size_out: int, xx: int):
+def _reference_weight(filter: str, t: float) -> float:
+    if filter == "box":
+        return 1.0 if -0.5 < t <= 0.5 else 0.0                   # of t itself: the asymmetry is Pillow's
+    t = abs(t)
+    if filter == "bilinear":
+        return 1.0 - t if t < 1.0 else 0.0
+    a = -0.5
+    if t < 1.0:
+        return ((a + 2.0) * t - (a + 3.0)) * t * t + 1.0
+    if t < 2.0:
+        return (((t - 5.0) * t + 8.0) * t - 4.0) * a
+    return 0.0
+
+
+def _reference_taps(size_in: int, size_out: int, xx: int, filter: str = "bilinear"):
     """(first source index, int coefficients) of output index ``xx``: Python floats are fp64, every operation rounded
     on its own."""
     scale = float(size_in) / size_out
     fs = max(scale, 1.0)
-    support, inv = fs, 1.0 / fs
+    support, inv = _SUPPORT[filter] * fs, 1.0 / fs
     center = (xx + 0.5) * scale
     xmin = max(int(center - support + 0.5), 0)
     xmax = min(int(center + support + 0.5), size_in)
     w, ww = [], 0.0
     for x in range(xmax - xmin):
-        a = abs((x + xmin - center + 0.5) * inv)
-        w.append(1.0 - a if a < 1.0 else 0.0)
+        w.append(_reference_weight(filter, (x + xmin - center + 0.5) * inv))
         ww += w[-1]
     if ww != 0.0:
         w = [v / ww for v in w]
-    return xmin, np.array([int(0.5 + v * 4194304.0) for v in w], dtype=np.int64)
+    return xmin, np.array([int(-0.5 + v * 4194304.0) if v < 0.0 else int(0.5 + v * 4194304.0) for v in w],
+                          dtype=np.int64)
 
 
-def _reference_pass(img: np.ndarray, size_out: int, first: int, count: int) -> np.ndarray:
-    """Output indices ``first .. first + count`` of the pass along axis 0 of ``img`` (n, ...) resized to ``size_out``."""
+def _reference_pass(img: np.ndarray, size_out: int, first: int, count: int, filter: str = "bilinear",
+                    extremes: Optional[list] = None) -> np.ndarray:
+    """Output indices ``first .. first + count`` of the pass along axis 0 of ``img`` (n, ...) resized to ``size_out``.
+    ``extremes``: a list ``[lowest, highest]`` of the unclamped accumulators seen so far, updated in place."""
     out = np.empty((count,) + img.shape[1:], dtype=np.uint8)
     shape = (-1,) + (1,) * (img.ndim - 1)
     for i in range(count):
-        xmin, k = _reference_taps(img.shape[0], size_out, first + i)
+        xmin, k = _reference_taps(img.shape[0], size_out, first + i, filter)
         acc = (1 << 21) + (k.reshape(shape) * img[xmin:xmin + len(k)].astype(np.int64)).sum(axis=0)
+        if extremes is not None and acc.size:
+            extremes[0], extremes[1] = min(extremes[0], int(acc.min())), max(extremes[1], int(acc.max()))
         out[i] = np.clip(acc >> 22, 0, 255)
     return out
 
 
-def resize_reference(image: np.ndarray, window, resized, rect=None) -> np.ndarray:
+def resize_reference(image: np.ndarray, window, resized, rect=None, filter: str = "bilinear",
+                     extremes: Optional[list] = None) -> np.ndarray:
     """The specification of ``include/basd_hip.h`` in numpy: ``image`` (H, W, C) uint8, ``window`` ``(win_x, win_y,
     win_w, win_h)``, ``resized`` ``(res_w, res_h)``, ``rect`` ``(out_x, out_y, OW, OH)`` (default: the whole resized
-    image).  Returns the rectangle as (OH, OW, C): the horizontal pass first, rounded to uint8, then the vertical one."""
+    image), ``filter`` one of ``INTERPOLATIONS``.  Returns the rectangle as (OH, OW, C): the horizontal pass first,
+    rounded to uint8, then the vertical one.  ``extremes``: a list ``[lowest, highest]`` that is updated with the
+    unclamped accumulators of both passes (what the tests use to show that a case reaches the clamp)."""
+    filter = _filter_name(filter)
     image = np.asarray(image)
     if image.ndim == 2:
         image = image[:, :, None]
@@ -418,5 +495,5 @@ def resize_reference(image: np.ndarray, window, resized, rect=None) -> np.ndarra
     out_x, out_y, OW, OH = (0, 0, res_w, res_h) if rect is None else (int(v) for v in rect)
     win = image[win_y:win_y + win_h, win_x:win_x + win_w]
     assert win.shape[:2] == (win_h, win_w) and out_x + OW <= res_w and out_y + OH <= res_h
-    horizontal = _reference_pass(win.transpose(1, 0, 2), res_w, out_x, OW).transpose(1, 0, 2)     # (win_h, OW, C)
-    return _reference_pass(horizontal, res_h, out_y, OH)
+    horizontal = _reference_pass(win.transpose(1, 0, 2), res_w, out_x, OW, filter, extremes).transpose(1, 0, 2)
+    return _reference_pass(horizontal, res_h, out_y, OH, filter, extremes)                        # from (win_h, OW, C)

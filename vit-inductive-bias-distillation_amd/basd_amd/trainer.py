@@ -103,6 +103,9 @@ class Trainer:
     augmented one (``RandomResizedCrop``) to ``config.model.vit.img_size`` with ``config.data.eval_crop_ratio``; it needs
     ``mixup="fused"`` and ``image_stats``.  The crops are drawn per step on the global CPU generator, or taken from the
     batch's optional ``"crop_params"`` entry (a ``CropParams``).  ``prepare_views(batch)`` returns the two batches.
+    ``resize_interpolation`` (it needs ``resize_crop``): ``"bilinear"`` (the default, the reference's), ``"bicubic"`` or
+    ``"box"``, or a dict per view such as ``{"clean": "bicubic", "augmented": "bilinear"}`` (the teacher's view resampled
+    the way a timm teacher was trained); still one launch.  ``evaluate`` resamples with the ``"clean"`` entry.
     ``jpeg_decode``: ``True`` (it needs ``resize_crop``) lets the batch's ``"images"`` be a ``JpegBatch`` of the files' bytes
     (the loader does not decode, ``collate_fn=collate_jpeg``): three launches of ``basd_amd.jpeg.JpegDecoder`` decode it
     into the ``RaggedBatch`` the resize launch takes; a ``RaggedBatch`` is taken as before.  ``"parallel"`` is ``True`` with
@@ -133,7 +136,7 @@ class Trainer:
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
                  resize_crop: bool = False, jpeg_decode=False, png_decode: bool = False, max_grad_norm=None,
-                 skip_nonfinite: bool = False, prefetch: int = 0) -> None:
+                 skip_nonfinite: bool = False, prefetch: int = 0, resize_interpolation="bilinear") -> None:
         if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
             raise ValueError(f"prefetch must be an int >= 0 (got {prefetch!r})")
         self._guarded = max_grad_norm is not None or bool(skip_nonfinite)
@@ -198,7 +201,11 @@ class Trainer:
         if resize_crop:
             self._require_fused("resize_crop needs", "it hands its uint8 batches to the fused launches")
             from .resize import ResizeCrop
-            self._resizer = ResizeCrop(config.model.vit.img_size, config.data.eval_crop_ratio, device=self.device)
+            self._resizer = ResizeCrop(config.model.vit.img_size, config.data.eval_crop_ratio, device=self.device,
+                                       interpolation=resize_interpolation)
+        elif resize_interpolation != "bilinear":
+            raise ValueError("resize_interpolation names the filter of the resize launch: it needs resize_crop=True; "
+                             f"got resize_crop=False and resize_interpolation={resize_interpolation!r}")
         self._decoder = None
         if not (isinstance(jpeg_decode, bool) or jpeg_decode == "parallel"):
             raise ValueError(f"jpeg_decode must be True, False or 'parallel', not {jpeg_decode!r}")

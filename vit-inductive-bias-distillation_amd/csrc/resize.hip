@@ -1,10 +1,13 @@
-// Pillow-exact crops and bilinear resizes of ragged uint8 HWC images into dense uint8 NCHW batches in ONE launch (the
-// contract and the specification are in include/basd_hip.h).
+// Pillow-exact crops and resizes (bilinear, bicubic, box; chosen per record) of ragged uint8 HWC images into dense uint8
+// NCHW batches in ONE launch (the contract and the specification are in include/basd_hip.h; the per-axis code -- taps,
+// tap count, record check -- is resize_core.h, which a host program compiles too).
 //
 // One workgroup of 8 waves per (band of output rows, record).  The record is uniform over the workgroup, so its
-// validation costs no divergence: a record outside its limits has its band zeroed and nothing of it is read.  Phases:
+// validation and its filter cost no divergence: a record outside its limits has its band zeroed and nothing of it is
+// read.  Phases:
 //   coefficients  the horizontal taps of the workgroup's columns and the vertical taps of its rows, one lane per column /
-//                 row, fp64 with contraction off, as integers of 22 fractional bits in LDS.  Each is made once.
+//                 row, fp64 with contraction off, as integers of 22 fractional bits in LDS.  Each is made once.  The
+//                 passes below only see integer taps (of either sign) and do not know the filter.
 //   horizontal    for the source rows the vertical taps of a run of output rows need: one lane per (row, column), the
 //                 C channels of a pixel together, bytes from global memory, the rounded byte into LDS (planar, pitch a
 //                 multiple of 4).  The run is as long as BASD_RESIZE_STAGE_BYTES allows (a band is cut where it does
@@ -12,25 +15,26 @@
 //   vertical      out of LDS, four neighbouring bytes of a row per lane through one 32-bit LDS read per tap, and one
 //                 32-bit store where the destination is aligned (single bytes otherwise and at a row's end).
 #include "basd_common.h"
-#include "../../include/basd_hip.h"
+#include "resize_core.h"
 
 namespace basd {
 
 constexpr int kResizeBlock = 512;
 constexpr int kResizeBandMax = 32;                                     // output rows of a workgroup
-constexpr int kResizeTapsMax = 2 * BASD_RESIZE_MAX_RATIO + 1;          // 65
 constexpr int kResizeColsMax = 1024;                                   // columns of a chunk
 constexpr int kResizeCoefInts = 4096;                                  // horizontal coefficients of a chunk
 constexpr int kResizeStage = BASD_RESIZE_STAGE_BYTES;
-constexpr int kResizeHxOff = 0;                                        // int2 (first tap, taps) per column
+constexpr int kResizeHxOff = 0;                                        // ResizeSpan (first tap, taps) per column
 constexpr int kResizeKhOff = kResizeHxOff + kResizeColsMax * 8;
-constexpr int kResizeVyOff = kResizeKhOff + kResizeCoefInts * 4;       // int2 per row
+constexpr int kResizeVyOff = kResizeKhOff + kResizeCoefInts * 4;       // ResizeSpan per row
 constexpr int kResizeKvOff = kResizeVyOff + kResizeBandMax * 8;
 constexpr int kResizeStageOff = (kResizeKvOff + kResizeBandMax * kResizeTapsMax * 4 + 15) & ~15;
 constexpr int kResizeLds = kResizeStageOff + kResizeStage;
 static_assert(kResizeLds <= 80 * 1024, "two workgroups share a CU's 160 KiB of LDS");
 static_assert(kResizeStage / (3 * kResizeTapsMax) >= 8, "the taps of one output row always fit the stage");
 static_assert(sizeof(BasdResizeRecord) == 64, "the record table has 64-byte rows");
+static_assert(offsetof(BasdResizeRecord, filter) == 48, "the filter took the first reserved word");
+static_assert(sizeof(ResizeSpan) == 8, "one 64-bit LDS read per span");
 
 struct ResizeArgs {
     const unsigned char* src;
@@ -41,67 +45,11 @@ struct ResizeArgs {
     int C, OH, OW, band, bands;
 };
 
-__device__ __forceinline__ int resize_ksize(int in, int out) {
-    // 2 ceil(support) + 1 with support = max(in / out, 1): the integer ceiling is that of the fp64 quotient
-    return 2 * (in > out ? (in + out - 1) / out : 1) + 1;
-}
-
-// The taps of output index xx: k[0 .. n) and the first source index (the formulas of the header, in their order).
-__device__ __forceinline__ int2 resize_taps(int in, int out, int xx, int ksize, int* k) {
-#pragma clang fp contract(off)
-    const double scale = (double)in / (double)out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double inv = 1.0 / fs;
-    const double center = ((double)xx + 0.5) * scale;
-    int lo = (int)((center - fs) + 0.5);
-    int hi = (int)((center + fs) + 0.5);
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > in ? in : hi;
-    int n = hi - lo;
-    n = n < 0 ? 0 : n > ksize ? ksize : n;
-    double ww = 0.0;
-    for (int x = 0; x < n; ++x) {
-        double a = (((double)(x + lo) - center) + 0.5) * inv;
-        a = a < 0.0 ? -a : a;
-        const double w = a < 1.0 ? 1.0 - a : 0.0;
-        ww = ww + w;
-    }
-    for (int x = 0; x < n; ++x) {
-        double a = (((double)(x + lo) - center) + 0.5) * inv;
-        a = a < 0.0 ? -a : a;
-        double w = a < 1.0 ? 1.0 - a : 0.0;
-        if (ww != 0.0) w = w / ww;
-        const double scaled = w * 4194304.0;
-        k[x] = (int)(0.5 + scaled);
-    }
-    return int2{lo, n};
-}
-
-__device__ __forceinline__ unsigned resize_clip(int acc) {
-    const int v = acc >> 22;
-    return v < 0 ? 0u : v > 255 ? 255u : (unsigned)v;
-}
-
-__device__ __forceinline__ int resize_check(const BasdResizeRecord& r, const ResizeArgs& a) {
-    const long lim = BASD_RESIZE_MAX_SIDE;
-    bool ok = r.src_h >= 1 && r.src_w >= 1 && r.src_h <= lim && r.src_w <= lim && r.res_h >= 1 && r.res_w >= 1 &&
-              r.res_h <= lim && r.res_w <= lim;
-    ok = ok && r.src_offset >= 0 && r.src_offset <= a.src_bytes &&
-         (long)r.src_h * r.src_w * a.C <= a.src_bytes - r.src_offset;               // sides <= 2^20: no overflow
-    ok = ok && r.win_x >= 0 && r.win_y >= 0 && r.win_w >= 1 && r.win_h >= 1 && (long)r.win_x + r.win_w <= r.src_w &&
-         (long)r.win_y + r.win_h <= r.src_h;
-    ok = ok && r.out_x >= 0 && r.out_y >= 0 && (long)r.out_x + a.OW <= r.res_w && (long)r.out_y + a.OH <= r.res_h;
-    if (!ok) return BASD_RESIZE_BAD_GEOMETRY;
-    if (r.win_w > (long)BASD_RESIZE_MAX_RATIO * r.res_w || r.win_h > (long)BASD_RESIZE_MAX_RATIO * r.res_h)
-        return BASD_RESIZE_BAD_RATIO;
-    return 0;
-}
-
 __global__ void __launch_bounds__(kResizeBlock) resize_crop_kernel(ResizeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int2* hx = (int2*)(smem + kResizeHxOff);
+    ResizeSpan* hx = (ResizeSpan*)(smem + kResizeHxOff);
     int* kh = (int*)(smem + kResizeKhOff);
-    int2* vy = (int2*)(smem + kResizeVyOff);
+    ResizeSpan* vy = (ResizeSpan*)(smem + kResizeVyOff);
     int* kv = (int*)(smem + kResizeKvOff);
     unsigned char* stage = smem + kResizeStageOff;
     const int tid = threadIdx.x;
@@ -112,7 +60,7 @@ __global__ void __launch_bounds__(kResizeBlock) resize_crop_kernel(ResizeArgs a)
     const int nrows = OH - y0 < a.band ? OH - y0 : a.band;
     unsigned char* d = a.dst + (long)rec * C * OH * OW;
 
-    const int bad = resize_check(r, a);
+    const int bad = resize_check(r, a.src_bytes, a.C, a.OH, a.OW);
     if (bad) {                                                         // uniform over the workgroup
         if (tid == 0 && band == 0) atomicOr(a.status, bad);
         const int per_plane = nrows * OW;
@@ -123,7 +71,8 @@ __global__ void __launch_bounds__(kResizeBlock) resize_crop_kernel(ResizeArgs a)
         return;
     }
 
-    const int ksh = resize_ksize(r.win_w, r.res_w), ksv = resize_ksize(r.win_h, r.res_h);
+    const int filter = r.filter;                                       // uniform, and one of the three
+    const int ksh = resize_ksize(r.win_w, r.res_w, filter), ksv = resize_ksize(r.win_h, r.res_h, filter);
     // columns of a chunk: the coefficient table, the column table and ksv rows of the stage hold them
     int cw = OW;
     cw = cw < kResizeCoefInts / ksh ? cw : kResizeCoefInts / ksh;
@@ -143,40 +92,43 @@ __global__ void __launch_bounds__(kResizeBlock) resize_crop_kernel(ResizeArgs a)
         // ---- coefficients (the rows' with the first chunk)
         const int items = cols + (x0 == 0 ? nrows : 0);
         for (int i = tid; i < items; i += kResizeBlock) {
-            if (i < cols) hx[i] = resize_taps(r.win_w, r.res_w, r.out_x + x0 + i, ksh, kh + i * ksh);
-            else vy[i - cols] = resize_taps(r.win_h, r.res_h, r.out_y + y0 + (i - cols), ksv, kv + (i - cols) * ksv);
+            if (i < cols) hx[i] = resize_taps(r.win_w, r.res_w, r.out_x + x0 + i, ksh, filter, kh + i * ksh);
+            else vy[i - cols] = resize_taps(r.win_h, r.res_h, r.out_y + y0 + (i - cols), ksv, filter,
+                                            kv + (i - cols) * ksv);
         }
         __syncthreads();
 
         for (int s = 0; s < nrows;) {
             // the longest run of output rows whose source rows fit the stage (first taps and ends do not decrease)
-            const int row0 = vy[s].x;
+            const int row0 = vy[s].first;
             int e = s + 1;
-            while (e < nrows && vy[e].x + vy[e].y - row0 <= max_rows) ++e;
-            int nsrc = vy[e - 1].x + vy[e - 1].y - row0;
-            nsrc = nsrc > max_rows ? max_rows : nsrc;                  // never: vy[s].y <= ksv <= max_rows
+            while (e < nrows && vy[e].first + vy[e].count - row0 <= max_rows) ++e;
+            int nsrc = vy[e - 1].first + vy[e - 1].count - row0;
+            nsrc = nsrc > max_rows ? max_rows : nsrc;                  // never: vy[s].count <= ksv <= max_rows
 
+            // Both passes multiply with __mul24 (v_mad_i32_i24, full rate; a 32-bit multiply is not): a coefficient is a
+            // signed 24-bit number (|w / ww| < 2, so |k| < 2^23) and a byte is one too, and the product is exact.
             // ---- horizontal: source rows row0 .. row0 + nsrc of the window -> stage
             for (int i = tid; i < nsrc * cols; i += kResizeBlock) {
                 const int rr = i / cols, col = i - rr * cols;
-                const int2 t = hx[col];
-                const unsigned char* p = window + (long)(row0 + rr) * src_pitch + (long)t.x * C;
+                const ResizeSpan t = hx[col];
+                const unsigned char* p = window + (long)(row0 + rr) * src_pitch + (long)t.first * C;
                 const int* k = kh + col * ksh;
                 unsigned char* q = stage + rr * pitch + col;
                 if (C == 3) {
                     int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
-                    for (int j = 0; j < t.y; ++j) {
+                    for (int j = 0; j < t.count; ++j) {
                         const int kk = k[j];
-                        a0 += kk * (int)p[3 * j];
-                        a1 += kk * (int)p[3 * j + 1];
-                        a2 += kk * (int)p[3 * j + 2];
+                        a0 += __mul24(kk, (int)p[3 * j]);
+                        a1 += __mul24(kk, (int)p[3 * j + 1]);
+                        a2 += __mul24(kk, (int)p[3 * j + 2]);
                     }
                     q[0] = (unsigned char)resize_clip(a0);
                     q[cwp] = (unsigned char)resize_clip(a1);
                     q[2 * cwp] = (unsigned char)resize_clip(a2);
                 } else {
                     int a0 = 1 << 21;
-                    for (int j = 0; j < t.y; ++j) a0 += k[j] * (int)p[j];
+                    for (int j = 0; j < t.count; ++j) a0 += __mul24(k[j], (int)p[j]);
                     q[0] = (unsigned char)resize_clip(a0);
                 }
             }
@@ -188,17 +140,17 @@ __global__ void __launch_bounds__(kResizeBlock) resize_crop_kernel(ResizeArgs a)
             for (int i = tid; i < (e - s) * C * groups; i += kResizeBlock) {
                 const int g = i % groups, yc = i / groups;
                 const int c = yc % C, y = s + yc / C;
-                const int2 t = vy[y];
-                const unsigned* q = (const unsigned*)(stage + (t.x - row0) * pitch + c * cwp) + g;
+                const ResizeSpan t = vy[y];
+                const unsigned* q = (const unsigned*)(stage + (t.first - row0) * pitch + c * cwp) + g;
                 const int* k = kv + y * ksv;
                 int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21, a3 = 1 << 21;
-                for (int j = 0; j < t.y; ++j) {
+                for (int j = 0; j < t.count; ++j) {
                     const unsigned w = q[j * pitch4];
                     const int kk = k[j];
-                    a0 += kk * (int)(w & 255u);
-                    a1 += kk * (int)((w >> 8) & 255u);
-                    a2 += kk * (int)((w >> 16) & 255u);
-                    a3 += kk * (int)(w >> 24);
+                    a0 += __mul24(kk, (int)(w & 255u));
+                    a1 += __mul24(kk, (int)((w >> 8) & 255u));
+                    a2 += __mul24(kk, (int)((w >> 16) & 255u));
+                    a3 += __mul24(kk, (int)(w >> 24));
                 }
                 const unsigned o0 = resize_clip(a0), o1 = resize_clip(a1), o2 = resize_clip(a2), o3 = resize_clip(a3);
                 unsigned char* dp = d + ((long)c * OH + y0 + y) * OW + x0 + 4 * g;
