@@ -231,6 +231,88 @@ int basd_tridiag_eigenvectors(const float* d, const float* e, const float* tau, 
                               const float* vals_desc, int n, int k, int batch, float* z, float* vecs, int k_stride,
                               hipStream_t stream);
 
+/* ---- opt-in residual check of a tridiagonal factorisation ------------------------------------------------------
+ * For a symmetric A of order n, its factorisation (d, e, tau, vh) and a probe vector x, with eps = 2^-24 and every sum
+ * accumulated in fp64:
+ *     rho_trace = |sum d_i - tr A| / (eps |A|_F)
+ *     rho_fro   = |sum d_i^2 + 2 sum e_i^2 - |A|_F^2| / (eps |A|_F^2)
+ *     rho_res   = |Q^T (A x) - T (Q^T x)|_2 / (eps |A|_F |x|_2),   Q the reflector product, T = tridiag(d, e).
+ * A numerator of exactly 0 over a denominator of 0 (the zero matrix) is ratio 0; a ratio that is not <= its threshold
+ * (any non-finite one included) fails.  The first two catch a wrong d or e, the third is a one-vector Freivalds test that
+ * also covers tau and vh.  All three are NORMWISE: an error confined to directions whose eigenvalues lie far below
+ * |A|_F is smaller than the rounding these bounds allow for and is not seen.
+ *
+ * The probe vector has no RNG state: element i of matrix index m (its position in the batch of the call) is
+ *     h  = m * MUL_M + i * MUL_I + ADD;  h ^= h >> 15;  h *= MIX_1;  h ^= h >> 12;  h *= MIX_2;  h ^= h >> 15;
+ *     x  = (h >> 31) ? -1 : +1                              (uint32 arithmetic; basd_tridiag_probe_sign below).
+ *
+ * Order of the calls on one stream: basd_tridiag_probe (reads A, which the factorisation destroys), basd_tridiag*,
+ * basd_tridiag_apply_q(tau, vh, n, 2, batch, probe, work, 2, 1) on the two rows the probe leaves, basd_tridiag_check.
+ * Three launches in all; no entry point allocates or synchronises. */
+#define BASD_TRIDIAG_PROBE_MUL_M 0x9E3779B1u
+#define BASD_TRIDIAG_PROBE_MUL_I 0x85EBCA77u
+#define BASD_TRIDIAG_PROBE_ADD 0x27D4EB2Fu
+#define BASD_TRIDIAG_PROBE_MIX_1 0x2C1B3C6Du
+#define BASD_TRIDIAG_PROBE_MIX_2 0x297A2D39u
+#define BASD_TRIDIAG_PROBE_ROWS 16          /* rows of A per workgroup of the probe launch */
+#define BASD_TRIDIAG_CHECK_MAX_N 1024       /* largest order (that of basd_tridiag_apply_q) */
+#define BASD_TRIDIAG_VERDICT_INTS 8
+/* Default thresholds (thresholds == NULL): 8 x the worst value measured over fp32 LAPACK ssytrd and this library's own
+ * factorisations, profiles/tridiag_check.txt.  The two sum tests grow like sqrt(n) (n rounded terms), the residual
+ * test does not.  How far they sit below a single-entry corruption (same file): a d entry moved by 1e-3 max|d| gives
+ * rho_trace 3.5 x its limit on a randn Gram of order 448, but only 16777 / sqrt(n) on a multiple of the identity -- 1.2 x
+ * the limit at order 1024, and nothing from order 1261 on; an e entry moved likewise 3.1 x the rho_res limit; a tau or
+ * vh entry of an active reflector moved by 1e-2 at least 13 x it on the matrices measured, about 2 x for the smallest
+ * such effect known (rho_res 38).  Not the factor 4 one would like: pass tighter limits where the matrices allow it. */
+#define BASD_TRIDIAG_CHECK_TRACE_PER_SQRT_N 13.3
+#define BASD_TRIDIAG_CHECK_FRO_PER_SQRT_N 8.5
+#define BASD_TRIDIAG_CHECK_RES 18.6
+#define BASD_TRIDIAG_CHECK_BIT_TRACE 1
+#define BASD_TRIDIAG_CHECK_BIT_FRO 2
+#define BASD_TRIDIAG_CHECK_BIT_RES 4
+
+#if defined(__HIPCC__)
+#define BASD_TRIDIAG_PROBE_FN static __host__ __device__ __forceinline__
+#else
+#define BASD_TRIDIAG_PROBE_FN static inline
+#endif
+BASD_TRIDIAG_PROBE_FN float basd_tridiag_probe_sign(uint32_t m, uint32_t i) {
+    uint32_t h = m * BASD_TRIDIAG_PROBE_MUL_M + i * BASD_TRIDIAG_PROBE_MUL_I + BASD_TRIDIAG_PROBE_ADD;
+    h ^= h >> 15;
+    h *= BASD_TRIDIAG_PROBE_MIX_1;
+    h ^= h >> 12;
+    h *= BASD_TRIDIAG_PROBE_MIX_2;
+    h ^= h >> 15;
+    return (h >> 31) ? -1.0f : 1.0f;
+}
+
+/* Bytes of the probe buffer of `batch` matrices of order n (16-byte aligned device memory; 0 = order not covered).
+ * Layout: (batch, 2, n) fp32 -- row 0 = x, row 1 = y = A x accumulated in fp64 and rounded once --, then per matrix
+ * ceil(n / BASD_TRIDIAG_PROBE_ROWS) pairs of fp64 (tr A, |A|_F^2 of that block of rows; basd_tridiag_check and
+ * the callers fold them in index order), then the fp64 pair (tr A, |A|_F^2) of every matrix folded in that order by
+ * basd_tridiag_check, then 8 control words for the verdict of basd_tridiag_check, which the probe launch clears. */
+long basd_tridiag_probe_bytes(int n, int batch);
+
+/* One pass over `batch` full row-major symmetric matrices (a_batch_stride elements apart), BEFORE basd_tridiag destroys
+ * them: one workgroup per BASD_TRIDIAG_PROBE_ROWS rows, 16-byte loads where n, the stride and the base allow, every
+ * reduction in a fixed order (two calls leave the same bits).  1 <= n <= BASD_TRIDIAG_CHECK_MAX_N, else
+ * BASD_EUNSUPPORTED. */
+int basd_tridiag_probe(const float* a, long a_batch_stride, int n, int batch, void* probe, hipStream_t stream);
+
+/* The three ratios of every matrix -> ratios_out (batch, 3) fp32, and the verdict of the batch -> verdict_out
+ * (BASD_TRIDIAG_VERDICT_INTS int32): [0] matrices that failed, [1] index of the first one (-1: none), [2] OR of their
+ * BASD_TRIDIAG_CHECK_BIT_* masks, [3] matrices checked, [4..6] the fp32 bit patterns of the worst rho_trace, rho_fro,
+ * rho_res of the batch (a NaN counts as worst), [7] 0.  host_mirror (nullable): pinned host memory that receives the same
+ * 8 words.  One workgroup per matrix; the last one to finish writes the verdict.
+ * work: (batch, 2, n) = Q^T of the probe's two rows (see above; NULL = Q is the identity, the rows are read from the
+ * probe itself: n == 1, for which there is no reflector and basd_tridiag_apply_q takes no call).  tau and vh are
+ * only checked for presence: they enter through `work`.  thresholds (host, nullable): rho_trace, rho_fro, rho_res
+ * limits; NULL = the defaults above.  A probe serves one check at a time (the control words are shared), any number one
+ * after another. */
+int basd_tridiag_check(const float* d, const float* e, const float* tau, const float* vh, int n, int batch,
+                       void* probe, const float* work, const float* thresholds, float* ratios_out, int* verdict_out,
+                       int* host_mirror, hipStream_t stream);
+
 /* ---- selector epilogues --------------------------------------------------------------------- */
 
 /* rank = min(#{eig > fp32(median_lower(eig) * factor)}, cap).  layer_selector.py:17-19, :74.

@@ -54,6 +54,9 @@ SIGNATURES = {
     "basd_tridiag_mp_rank": [vp, vp, i32, i32, f64, i32, vp, vp, vp, vp, vp],
     "basd_tridiag_mp_rank_rank1": [vp, vp, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp],
     "basd_tridiag_eigenvectors": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp],
+    "basd_tridiag_probe_bytes": [i32, i32],
+    "basd_tridiag_probe": [vp, i64, i32, i32, vp, vp],
+    "basd_tridiag_check": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "basd_mp_rank": [vp, i32, i32, f64, i32, vp, vp, vp],
     "basd_grassmann_distance": [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp],
     "basd_grassmann_distance_padded": [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp],
@@ -182,7 +185,8 @@ EINVAL, EUNSUPPORTED = -1, -2        # BASD_EINVAL / BASD_EUNSUPPORTED of includ
 # sizing helpers declared `long` in include/basd_hip.h
 LONG_RESULTS = {"basd_tridiag_workspace_bytes", "basd_jacobi_twopass_workspace_bytes",
                 "basd_mix_grad_tokens_scratch_floats", "basd_teacher_center_stream_scratch_floats",
-                "basd_rank_certificate_scratch_bytes", "basd_sfadamw_launches", "basd_jpeg_status_bytes", "basd_png_status_bytes"}
+                "basd_rank_certificate_scratch_bytes", "basd_sfadamw_launches", "basd_jpeg_status_bytes", "basd_png_status_bytes",
+                "basd_tridiag_probe_bytes"}
 
 _lock = threading.Lock()
 _lib = None

@@ -50,6 +50,22 @@ def marchenko_pastur_rank(features: torch.Tensor) -> int:
     features = ops.as_supported(features)
     M, D = features.shape
     gram = _uncentred_gram(features).unsqueeze(0).contiguous()
+    checked = check_switch()          # (``capture.estimate_intrinsic_dim`` comes through here too)
+    if checked and not (ops.EIG_SOLVER == "tridiag" and 2 <= gram.shape[1] <= 1024):
+        global _UNCHECKED_WARNED
+        if not _UNCHECKED_WARNED:
+            import warnings
+            _UNCHECKED_WARNED = True
+            warnings.warn("marchenko_pastur_rank: BASD_TRIDIAG_CHECK=1 but this eigen-solve is NOT checked: the residual "
+                          f"check covers tridiagonal factorisations of orders 2..1024 (order {gram.shape[1]}, "
+                          f"EIG_SOLVER = {ops.EIG_SOLVER!r}); said once per process", RuntimeWarning)
+        checked = False
+    if checked:
+        ts = ops.tridiagonalise(gram, check=True)
+        rank = ops.mp_rank_device(ops.tridiag_spectrum(ts), M, D, cap=1 << 30)
+        words = torch.cat([rank.to(torch.int32), ts.check.verdict]).tolist()          # the one wait this function has
+        _raise_if_check_failed(ts.check, words[1:], "uncentred-Gram")
+        return int(words[0])
     vals = _eigenvalues_desc(gram)
     rank = ops.mp_rank_device(vals, M, D, cap=1 << 30)
     return int(rank.item())
@@ -113,6 +129,39 @@ class TridiagGiveUp(RuntimeError):
     """Workgroups sharing a matrix in the tridiagonalisation's first stage lost each other (bounded spin): the eigen-
     solve results of this step are invalid.  The callers re-queue the step's selector with ONE workgroup per matrix
     (nothing waits for anything then) and keep that setting: a slower selector instead of a dead training run."""
+
+
+class TridiagCheckFailed(TridiagGiveUp):
+    """A factorisation failed its residual check (``check_factorisations``; include/basd_hip.h: rho_trace, rho_fro,
+    rho_res against their thresholds).  Handled like the give-up it derives from: the step's selector is queued once
+    more with one workgroup per matrix; a second failure in the same step propagates.  ``matrix``: index of the first
+    failing matrix in its factorisation launch; ``ratios``: its three ratios; ``bits``: OR of the failing tests
+    (``ops.CHECK_BITS``) over the launch's failing matrices."""
+
+    def __init__(self, where: str, matrix: int, ratios, bits: int, failed: int, checked: int):
+        self.matrix, self.ratios, self.bits = int(matrix), tuple(float(r) for r in ratios), int(bits)
+        names = [n for k, n in enumerate(ops.CHECK_BITS) if bits >> k & 1]
+        super().__init__(f"basd_tridiag: {failed} of {checked} {where} factorisations failed the residual check "
+                         f"({', '.join(names)}); first: matrix {matrix} with rho_trace, rho_fro, rho_res = "
+                         f"{self.ratios[0]:.3g}, {self.ratios[1]:.3g}, {self.ratios[2]:.3g}")
+
+
+def check_switch() -> bool:
+    """BASD_TRIDIAG_CHECK=1: residual check of every tridiagonal factorisation.  The selector reads it once, at
+    construction, into ``check_factorisations`` (as its neighbouring switches are read); ``marchenko_pastur_rank`` has
+    no object to keep it on and reads it at every call."""
+    return os.environ.get("BASD_TRIDIAG_CHECK", "0") == "1"
+
+
+_UNCHECKED_WARNED = False        # marchenko_pastur_rank said once that the switch is on and its eigen-solve unchecked
+
+
+def _raise_if_check_failed(verdict: "ops.TridiagVerdict", words: list[int], where: str) -> None:
+    """``words``: the verdict's 8 ints on the host (its pinned mirror, complete).  The failing matrix's ratios are
+    fetched from the device here: a wait, on the failure path only."""
+    if words[0]:
+        ratios = verdict.ratios[words[1]].tolist()
+        raise TridiagCheckFailed(where, words[1], ratios, words[2], words[0], words[3])
 
 
 def _single_member_mode(why: str) -> None:
@@ -460,6 +509,14 @@ class GrassmannianLayerSelector(nn.Module):
         self.teacher_space_gram = os.environ.get("BASD_TEACHER_SPACE_GRAM", "1") != "0"
         self.rank1_mp = os.environ.get("BASD_RANK1_MP", "1") != "0"
         self.merge_factorisations = os.environ.get("BASD_MERGE_FACTORISATIONS", "1") != "0"   # cfg-4: 46.4 -> ? ms
+        # opt-in residual check of every factorisation of the kernel-by-kernel layout (BASD_TRIDIAG_CHECK=1): three
+        # launches around each ``ops.tridiagonalise``, the verdict read with the ranks; a failure raises
+        # ``TridiagCheckFailed``.  ``BASDLoss`` keeps single-teacher steps on that layout while this is on.
+        self.check_factorisations = check_switch()
+        # what the latest read-back read (switch on): worst = the worst rho_trace, rho_fro, rho_res, checked = matrices,
+        # of which `late` are the PREVIOUS step's student matrices (single-teacher steps: nothing of a step waits for its
+        # student side, whose verdict is read with the next step's ranks, or by ``finish_pending``)
+        self.last_check: dict | None = None
         # backward of multi-layer teachers at student orders the LDS-resident Jacobi solver takes: full Jacobi eigenvectors
         # (see ``_spectra_async``); False keeps the tridiagonal route of larger students (tests cover it at small shapes)
         self.small_student_jacobi = True
@@ -497,6 +554,8 @@ class GrassmannianLayerSelector(nn.Module):
         pending, self._pending_tail = self._pending_tail, None
         if pending is not None:
             pending()
+        if self.__dict__.get("_pending_checks"):      # the student-side verdict that no later step has read yet
+            self._read_checks(dict(checks=[]))
 
     # ---- teacher side: ranks + subspaces -------------------------------------------------
     @torch.no_grad()
@@ -618,7 +677,20 @@ class GrassmannianLayerSelector(nn.Module):
         # students (cfg-4's 768) keep the tridiagonal route.
         stud_jacobi = not tri or (all_student_vectors and self.small_student_jacobi
                                   and bool(ops._lib.query("basd_jacobi_lds_square_fits", d_s)))
-        st = dict(E=E, L=L, tri=tri, stud_jacobi=stud_jacobi, student_stream=student_stream)
+        st = dict(E=E, L=L, tri=tri, stud_jacobi=stud_jacobi, student_stream=student_stream, checks=[])
+
+        def check_arg(slot: str):
+            """``check=`` of a factorisation: off, or the pinned mirror of its verdict"""
+            return self._pinned_ints("check_" + slot, ops.VERDICT_INTS) if self.check_factorisations else False
+
+        def checked(ts, where: str, deferred: bool = False):
+            """note a checked factorisation for ``_read_ranks`` (``deferred``: with the student side's status word, one
+            step later); the event is recorded on the stream that ran it, behind its check"""
+            if ts.check is not None:
+                ev = torch.cuda.Event()
+                ev.record()
+                st["checks"].append(dict(verdict=ts.check, event=ev, where=where, deferred=deferred))
+            return ts
 
         cur = torch.cuda.current_stream()
         projected = None
@@ -658,7 +730,8 @@ class GrassmannianLayerSelector(nn.Module):
                 elif stud_jacobi:
                     st["s_stack"], st["s_colnorm"] = s_stack, ops.jacobi_onesided(s_stack, d_s)
                 else:
-                    s_ts = ops.tridiagonalise(s_stack)
+                    s_ts = checked(ops.tridiagonalise(s_stack, check=check_arg("student")), "student",
+                                   deferred=student_stream is not None)
                     if student_stream is not None:
                         # status word of this factorisation: read by the host one step later (it never waits
                         # for the student chain)
@@ -688,7 +761,7 @@ class GrassmannianLayerSelector(nn.Module):
             ops.gpu_mark("teacher_grams")
             st["o_c"] = 0
             pin = self._pinned_ints("teacher", L + 8)
-            ts = ops.tridiagonalise(g_all)
+            ts = checked(ops.tridiagonalise(g_all, check=check_arg("merged")), "teacher + student")
             t_ts = ops.tridiag_slice(ts, 0, L)
             w = ops.tridiag_apply_q(t_ts, self._teacher_zbar.view(L, 1, d_s).contiguous(), transpose=True)
             st["t_ts"], st["s_ts"] = t_ts, ops.tridiag_slice(ts, L, E)
@@ -715,7 +788,7 @@ class GrassmannianLayerSelector(nn.Module):
             # its basis as a rank-one modification: z^T z = Q (T + M w w^T) Q^T, w = Q^T zbar (basd_tridiag_mp_rank_rank1)
             st["o_c"] = 0
             pin = self._pinned_ints("teacher", L + 8)
-            ts = ops.tridiagonalise(g_c.contiguous())
+            ts = checked(ops.tridiagonalise(g_c.contiguous(), check=check_arg("teacher")), "teacher")
             w = ops.tridiag_apply_q(ts, self._teacher_zbar.view(L, 1, d_s).contiguous(), transpose=True)
             st["t_ts"] = ts
             st["ranks_dev"] = ops.tridiag_mp_rank_rank1(ts, w.view(L, d_s), M, d_s, d_s - 1, pin)
@@ -743,7 +816,8 @@ class GrassmannianLayerSelector(nn.Module):
                 if getattr(self, "_gate_event", None) is None:
                     self._gate_event = ops.new_event()
                 gate = self._gate_event
-            ts = ops.tridiagonalise(t_stack, mp_rank=(M, d_s, d_s - 1, L, pin, gate))
+            ts = checked(ops.tridiagonalise(t_stack, mp_rank=(M, d_s, d_s - 1, L, pin, gate), check=check_arg("teacher")),
+                         "teacher")
             st["t_ts"] = ts
             st["ranks_dev"] = ts.ranks
             ops.gpu_mark("ranks_ready")
@@ -830,11 +904,42 @@ class GrassmannianLayerSelector(nn.Module):
         if any(status):
             raise TridiagGiveUp("basd_tridiag: workgroups sharing a matrix timed out waiting for each other "
                                 f"(device oversubscribed?); eigen-solve results are invalid [{host[L:]}]")
+        if st.get("checks") or self.__dict__.get("_pending_checks"):
+            self._read_checks(st)
         for k, r in zip(keys, ranks):
             self._subspace_ranks[k] = r
         if min(ranks) == 0:
             raise _rank_zero_error()
         return ranks
+
+    def _read_checks(self, st: dict) -> None:
+        """The verdicts of the step's checked factorisations, from their pinned mirrors.  Their events lie on the streams
+        the ranks (or the status words) were just waited for, in front of what was waited for: no wait of its own.  A
+        student-side factorisation that nothing of this step waits for is read one step later, with its status word
+        (or by ``finish_pending``).  Late and current verdicts are decided separately: a late failure warns and degrades
+        (its eigenvectors only fed the previous step's principal angles, which nothing observed: nothing to redo), and
+        the first failure of THIS step is raised whatever the late ones said."""
+        late, self._pending_checks = self.__dict__.get("_pending_checks") or [], [c for c in st["checks"] if c["deferred"]]
+        current = [c for c in st["checks"] if not c["deferred"]]
+        st["checks"] = []
+        worst, counts, failures = [0.0, 0.0, 0.0], [0, 0], [None, None]
+        for which, entries in enumerate((late, current)):
+            for c in entries:
+                c["event"].synchronize()
+                words = c["verdict"].mirror.tolist()
+                counts[which] += words[3]
+                for k, r in enumerate(torch.tensor(words[4:7], dtype=torch.int32).view(torch.float32).tolist()):
+                    if worst[k] == worst[k] and (r != r or r > worst[k]):          # a NaN is the worst and stays
+                        worst[k] = r
+                if words[0] and failures[which] is None:
+                    failures[which] = (c, words)
+        self.last_check = dict(worst=tuple(worst), checked=sum(counts), late=counts[0])
+        if failures[0] is not None:
+            _single_member_mode(f"{failures[0][1][0]} student-side factorisation(s) of the previous step failed the "
+                                f"residual check (first: matrix {failures[0][1][1]})")
+        if failures[1] is not None:
+            c, words = failures[1]
+            _raise_if_check_failed(c["verdict"], words, c["where"])
 
     @torch.no_grad()
     def _angles_from_spectra(self, st: dict, keys: list[int], want_grad: bool = False,
@@ -1175,11 +1280,15 @@ class BASDLoss(nn.Module):
 
         def read_ranks_once():
             # The host reads the ranks here (and raises on rank 0 like the reference).
-            if "rank_ready" in spectra:
-                return sel._read_ranks(spectra, keys)               # waits on the rank kernel's event
-            with torch.cuda.stream(side):                           # plain read-back behind both chains
-                side.wait_stream(side2)
-                return sel._read_ranks(spectra, keys)
+            try:
+                if "rank_ready" in spectra:
+                    return sel._read_ranks(spectra, keys)               # waits on the rank kernel's event
+                with torch.cuda.stream(side):                           # plain read-back behind both chains
+                    side.wait_stream(side2)
+                    return sel._read_ranks(spectra, keys)
+            finally:
+                if sel.check_factorisations:
+                    comp["tridiag_check"] = sel.last_check
 
         def read_ranks():
             nonlocal spectra, chain_done
@@ -1361,7 +1470,10 @@ class BASDLoss(nn.Module):
         sel = self.layer_selector
         comp: dict[str, torch.Tensor] = {}          # this step's ``last_components`` (the selector tail fills d_grass_sq)
         selector_tail = None
-        if len(keys) == 1 and self.use_chain and SelectorChainPlan.supported(students, teachers):
+        # (``check_factorisations``: the checks sit around the launches of the kernel-by-kernel layout; basd_selector_chain
+        # has none, so single-teacher steps leave it while the switch is on, exactly as with BASD_SELECTOR_CHAIN=0)
+        if (len(keys) == 1 and self.use_chain and not sel.check_factorisations
+                and SelectorChainPlan.supported(students, teachers)):
             total, ce_loss, geo_layers, mix = self._forward_single_teacher(student_output, targets, students, keys,
                                                                            teachers, attns, comp)
         elif len(keys) == 1:
@@ -1375,6 +1487,8 @@ class BASDLoss(nn.Module):
                                                  *students)
             total = _UWSOCombine.apply(ce_loss, geo_layers)
             comp["d_grass_sq"] = sel._last_d_grass_sq
+            if sel.check_factorisations:
+                comp["tridiag_check"] = sel.last_check
         comp.update(ce=ce_loss.detach(), geo_layers=geo_layers.detach(), mix=mix.detach())
         self.last_components = comp
         ops.trace("combine_queued")

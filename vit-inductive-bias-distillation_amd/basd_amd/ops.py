@@ -300,26 +300,116 @@ class TridiagState:
     err: torch.Tensor | None = None   # (8,) int32; [0] non-zero if the workgroups sharing a matrix lost each other
                                       # ([1:6] then: step + 1, row, member | matrix << 8, tag seen, tag wanted)
     ranks: torch.Tensor | None = None   # Marchenko-Pastur ranks of the leading matrices (``tridiagonalise(mp_rank=)``)
+    check: "TridiagVerdict | None" = None   # residual check of the batch (``tridiagonalise(check=)``)
+
+
+PROBE_ROWS = 16          # BASD_TRIDIAG_PROBE_ROWS of include/basd_hip.h: rows of A per workgroup of the probe launch
+VERDICT_INTS = 8         # BASD_TRIDIAG_VERDICT_INTS
+CHECK_BITS = ("rho_trace", "rho_fro", "rho_res")       # BASD_TRIDIAG_CHECK_BIT_* = 1 << index
+
+
+@dataclass
+class TridiagProbe:
+    """What ``basd_tridiag_probe`` leaves of a batch of matrices before their factorisation destroys them (layout:
+    basd_tridiag_probe_bytes).  Views into one buffer; nothing here waits for the device."""
+    buf: torch.Tensor       # uint8
+    n: int
+    batch: int
+
+    @property
+    def rows(self) -> torch.Tensor:
+        """(batch, 2, n) fp32: x (the hashed signs) and y = A x."""
+        return self.buf[:self.batch * 2 * self.n * 4].view(torch.float32).view(self.batch, 2, self.n)
+
+    @property
+    def parts(self) -> torch.Tensor:
+        """(batch, ceil(n / PROBE_ROWS), 2) fp64: tr A and |A|_F^2 of every block of rows."""
+        n_parts = -(-self.n // PROBE_ROWS)
+        off = (self.batch * 2 * self.n * 4 + 15) & ~15
+        return self.buf[off:off + self.batch * n_parts * 16].view(torch.float64).view(self.batch, n_parts, 2)
+
+    @property
+    def sums(self) -> torch.Tensor:
+        """(batch, 2) fp64: tr A and |A|_F^2, folded from ``parts`` in index order by ``tridiag_check``."""
+        off = ((self.batch * 2 * self.n * 4 + 15) & ~15) + self.batch * (-(-self.n // PROBE_ROWS)) * 16
+        return self.buf[off:off + self.batch * 16].view(torch.float64).view(self.batch, 2)
+
+
+@dataclass
+class TridiagVerdict:
+    """Outcome of ``tridiag_check``, all on the device: ``ratios`` (batch, 3) fp32 = rho_trace, rho_fro, rho_res per
+    matrix; ``verdict`` (8,) int32 = failing matrices, index of the first (-1), OR of their CHECK_BITS masks, matrices
+    checked, fp32 bit patterns of the batch's worst three ratios, 0.  ``mirror``: the pinned host copy of ``verdict``
+    when one was asked for -- valid once an event recorded behind the check has completed."""
+    ratios: torch.Tensor
+    verdict: torch.Tensor
+    mirror: torch.Tensor | None = None
+
+    def read(self) -> dict:
+        """Host view (WAITS for the device): failed, first, bits, checked, worst (3 floats), ratios (batch, 3)."""
+        v = self.verdict.cpu()
+        return dict(failed=int(v[0]), first=int(v[1]), bits=int(v[2]), checked=int(v[3]),
+                    worst=v[4:7].view(torch.float32).tolist(), ratios=self.ratios.cpu())
+
+
+def tridiag_probe(G: torch.Tensor) -> TridiagProbe:
+    """Queue the probe launch over G (batch, n, n) symmetric fp32 contiguous -- BEFORE ``tridiagonalise`` destroys it."""
+    _require_cuda(G)
+    assert G.dtype == torch.float32 and G.is_contiguous() and G.dim() == 3 and G.shape[1] == G.shape[2]
+    batch, n, _ = G.shape
+    size = _lib.query("basd_tridiag_probe_bytes", n, batch)
+    if size <= 0:
+        raise RuntimeError(f"basd_tridiag_probe: order {n} is not covered (1..1024)")
+    buf = torch.empty((size,), device=G.device, dtype=torch.uint8)
+    _lib.call("basd_tridiag_probe", G.data_ptr(), n * n, n, batch, buf.data_ptr(), _stream())
+    return TridiagProbe(buf, n, batch)
+
+
+def tridiag_check(ts: TridiagState, probe: TridiagProbe, thresholds=None,
+                  host_mirror: torch.Tensor | None = None) -> TridiagVerdict:
+    """Queue the residual check of the factorisations ``ts`` against the probe of their matrices: Q^T of the probe's two
+    rows (``basd_tridiag_apply_q``, unchanged) and the check launch.  Device tensors; no host wait.  ``thresholds``:
+    (rho_trace, rho_fro, rho_res) limits, None = the library's defaults for the order (include/basd_hip.h).
+    ``host_mirror``: pinned int32 host tensor of VERDICT_INTS elements that also receives the verdict."""
+    batch, n = ts.d.shape
+    assert probe.n == n and probe.batch == batch, "the probe belongs to another batch"
+    assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (ts.d, ts.e, ts.tau, ts.vh))
+    work = tridiag_apply_q(ts, probe.rows, transpose=True) if n > 1 else None      # order 1: no reflector, Q = I
+    ratios = torch.empty((batch, 3), device=ts.d.device, dtype=torch.float32)
+    verdict = torch.empty((VERDICT_INTS,), device=ts.d.device, dtype=torch.int32)
+    thr = None
+    if thresholds is not None:
+        import ctypes
+        thr = (ctypes.c_float * 3)(*[float(t) for t in thresholds])
+    if host_mirror is not None:
+        assert host_mirror.is_pinned() and host_mirror.dtype == torch.int32 and host_mirror.numel() == VERDICT_INTS
+    _lib.call("basd_tridiag_check", ts.d.data_ptr(), ts.e.data_ptr(), ts.tau.data_ptr(), ts.vh.data_ptr(), n, batch,
+              probe.buf.data_ptr(), _ptr(work), thr, ratios.data_ptr(), verdict.data_ptr(), _ptr(host_mirror), _stream())
+    return TridiagVerdict(ratios, verdict, host_mirror)
 
 
 def tridiag_slice(ts: TridiagState, first: int, count: int) -> TridiagState:
     """Factorisations [first, first + count) of a batch as a state of their own (views; the status words are the
     batch's: one launch factored them all)."""
     sl = slice(first, first + count)
-    return TridiagState(ts.d[sl], ts.e[sl], ts.tau[sl], ts.vh[sl], ts.vals[sl], ts.err, None)
+    return TridiagState(ts.d[sl], ts.e[sl], ts.tau[sl], ts.vh[sl], ts.vals[sl], ts.err, None, ts.check)
 
 
-def tridiagonalise(G: torch.Tensor, mp_rank: tuple | None = None) -> TridiagState:
+def tridiagonalise(G: torch.Tensor, mp_rank: tuple | None = None, check=False) -> TridiagState:
     """G (batch, n, n) symmetric, DESTROYED.  Queues the Householder tridiagonalisation; ``vals`` is allocated but
     not filled (``tridiag_spectrum``).  No host sync.
     ``mp_rank`` = (M, D, cap, count, host_mirror | None[, mid_event handle | None]): also the Marchenko-Pastur ranks of the first ``count``
     matrices (``ts.ranks``, int32 on device), from the kernel that finishes the factorisation; ``host_mirror``: pinned
     int32 host tensor of count + 8 elements filled with the ranks and the status words (read it after an event
-    recorded behind this call)."""
+    recorded behind this call).
+    ``check``: True, or a pinned int32 host tensor of VERDICT_INTS elements for the verdict's host copy: the probe launch
+    is queued ahead of the factorisation and ``tridiag_check`` behind it, on the same stream, and the verdict hangs on
+    ``ts.check`` (three more launches; the factorisation's own launches and bits are those of ``check=False``)."""
     _require_cuda(G)
     assert G.dtype == torch.float32 and G.is_contiguous() and G.dim() == 3 and G.shape[1] == G.shape[2]
     batch, n, _ = G.shape
     f32 = dict(device=G.device, dtype=torch.float32)
+    probe = tridiag_probe(G) if check is not False else None
     d, e, tau = (torch.empty((batch, n), **f32) for _ in range(3))
     vh = torch.empty((batch, n, n), **f32)
     vals = torch.empty((batch, n), **f32)
@@ -337,7 +427,10 @@ def tridiagonalise(G: torch.Tensor, mp_rank: tuple | None = None) -> TridiagStat
         _lib.call("basd_tridiag_ranked", G.data_ptr(), n * n, n, batch, d.data_ptr(), e.data_ptr(), tau.data_ptr(),
                   vh.data_ptr(), work.data_ptr(), count, factor, cap, ranks.data_ptr(), _ptr(mirror), mid_event,
                   _stream())
-    return TridiagState(d, e, tau, vh, vals, work[-32:].view(torch.int32), ranks)
+    ts = TridiagState(d, e, tau, vh, vals, work[-32:].view(torch.int32), ranks)
+    if probe is not None:
+        ts.check = tridiag_check(ts, probe, host_mirror=check if isinstance(check, torch.Tensor) else None)
+    return ts
 
 
 def new_event() -> int:

@@ -136,7 +136,8 @@ class Trainer:
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
                  resize_crop: bool = False, jpeg_decode=False, png_decode: bool = False, max_grad_norm=None,
-                 skip_nonfinite: bool = False, prefetch: int = 0, resize_interpolation="bilinear") -> None:
+                 skip_nonfinite: bool = False, prefetch: int = 0, resize_interpolation="bilinear",
+                 check_factorisations: bool = False) -> None:
         if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
             raise ValueError(f"prefetch must be an int >= 0 (got {prefetch!r})")
         self._guarded = max_grad_norm is not None or bool(skip_nonfinite)
@@ -158,6 +159,10 @@ class Trainer:
             student_depth=student_info["depth"], num_student_tokens=student_info["num_tokens"], config=config.basd,
             teacher_has_cls_token=teacher.has_cls_token,
         ).to(self.device)
+        if check_factorisations:
+            # residual check of every tridiagonal factorisation of the selector (``TridiagCheckFailed``; the environment
+            # switch BASD_TRIDIAG_CHECK=1 sets the same attribute when the loss is built)
+            self.basd_loss.layer_selector.check_factorisations = True
         if optimizer == "adamw":
             self.optimizer = torch.optim.AdamW(student_model.parameters(), lr=config.training.learning_rate,
                                                weight_decay=config.training.weight_decay)
