@@ -830,7 +830,7 @@ __global__ void __launch_bounds__(1024) chol_f64_blocked_kernel(const double* __
 
 // ---------------------------------------------------------------------------
 // W[b] = [ L_a^T L_b ; L_b ]   (2n x n, column-major fp32, leading dimension 2n), fp64 accumulate.
-// stack_product_kernel: grid = batch, block = 256, both factors in LDS (n <= 98).
+// stack_product_kernel: grid = batch, block = 256, both factors in LDS (16 n^2 bytes <= 78 KB: n <= 70).
 // stack_product_global_kernel: grid = (ceil(n/32), ceil(n/32), batch), tiles of the factors through LDS (larger n).
 // ---------------------------------------------------------------------------
 // 32 x 32 output tiles, both factors staged through LDS in fp64; the zeros stored above the diagonals make
