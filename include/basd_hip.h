@@ -609,7 +609,8 @@ int basd_procrustes_forward_fused(const BasdProcrustesArgs* args, hipStream_t st
 /* The routes basd_procrustes_forward_fused takes for `args` under the current hooks (host only: no HIP call, usable
  * without a GPU; pointers are tested for presence and 16-byte alignment, never dereferenced, so any non-null aligned
  * value stands for "offered").  One planner (csrc/procrustes_plan.h) answers here and in the call.  out20:
- *    0 teacher centring: 1 stream, four features per thread; 2 stream; 3 all groups in one launch; 4 per group
+ *    0 teacher centring: 1 stream, four features per thread; 2 stream; 3 all groups in one launch; 4 per group;
+ *      5 given (basd_procrustes_plan_query_cached only)
  *    1 student projection: 1 all layers in one launch, 2 per layer;  2 features per trace slab (32 / 64);  3 slabs
  *    4 teacher Gram split (0 / 1);  5 Cholesky: 1 in LDS, 2 blocked;  6 cores: 1 transposed, 2 stacked [M; L_b]
  *    7 SVD: 1 one-sided Jacobi on the transposed cores, 2 basd_jacobi_stacked_twopass with jac_ws (one-sided where
@@ -622,6 +623,38 @@ int basd_procrustes_forward_fused(const BasdProcrustesArgs* args, hipStream_t st
  *   14..19 dynamic LDS bytes of the centring, projection, Gram, Cholesky, finish and fused-gradient kernels (0: none)
  * A stage with no route is 0 and the status BASD_EUNSUPPORTED; arguments the call rejects give BASD_EINVAL. */
 int basd_procrustes_plan_query(const BasdProcrustesArgs* args, long* out20);
+
+/* ---- the teacher side of a single-layer teacher, given instead of computed ------------------------------------
+ * With one teacher layer (L == 1, G == 1) the mixing weight is exactly 1 (layer_selector.py:110-112: softmax over one
+ * distance), so the teacher enters relational.py:22-39 only through three per-sample arrays that are a function of the
+ * teacher's input image alone: the fp64 Gram of the centred, weighted teacher tokens on the core grid (the teacher
+ * slot of g_all, rows E*B .. E*B + B), omega (B, n_s) and omega_t (B, n).
+ *
+ * basd_procrustes_forward_cached is basd_procrustes_forward_fused for G == 1 with those three as INPUTS: tok_ptrs,
+ * attn_ptrs, mix, mu_t, tc and g_slabs are not read, basd_token_weights, basd_teacher_center* and the teacher's
+ * basd_gram_f64(_split) are not queued, and everything from the student projection on -- student Grams, ONE Cholesky
+ * launch over all (E + 1) B matrices, cores, SVD, finish, UW-SO, student gradient -- is queued in the same order by the
+ * same routes, so with the same three arrays every output has the bits of the uncached call.  G != 1: BASD_EINVAL.
+ * basd_procrustes_plan_query_cached answers for it from the same planner: field 0 is 5 ("given"), fields 4, 13 and 14
+ * are 0, every other field is what basd_procrustes_plan_query answers for the same argument block. */
+int basd_procrustes_forward_cached(const BasdProcrustesArgs* args, hipStream_t stream);
+int basd_procrustes_plan_query_cached(const BasdProcrustesArgs* args, long* out20);
+/* The cache of those arrays, one row per dataset image: cache_g (capacity, n, n) fp64, cache_omega (capacity, n_s),
+ * cache_omega_t (capacity, n), all dense.  One launch each:
+ *   basd_teacher_cache_store scatters the B rows a call has just produced (g (B, n, n), omega (B, n_s), omega_t (B, n),
+ *     dense) into the cache rows index[b]; basd_teacher_cache_load gathers the cache rows index[b] into row b of the
+ *     places the cached call reads.
+ * index: (B) int64 on the device.  Offsets are formed in 64 bits (capacity * n * n * 8 passes 2^32 for real datasets).
+ * The Grams move as 16-byte pairs where n * n is even and both Gram bases are 16-byte aligned, as doubles otherwise
+ * (n = 49).  An index outside [0, capacity) copies nothing (callers check on the host).  A repeated index is legal in
+ * load.  In store, launches with equal indices race on that row: hand over EQUAL rows for them (the teacher side is a
+ * function of the image), then every interleaving leaves the same bytes.  B <= 65535. */
+int basd_teacher_cache_store(const double* g, const float* omega, const float* omega_t, const long* index, int B, int n,
+                             int n_s, long capacity, double* cache_g, float* cache_omega, float* cache_omega_t,
+                             hipStream_t stream);
+int basd_teacher_cache_load(const double* cache_g, const float* cache_omega, const float* cache_omega_t,
+                            const long* index, int B, int n, int n_s, long capacity, double* g, float* omega,
+                            float* omega_t, hipStream_t stream);
 /* Test / tuning hook, read by the planner: 0 = always the stacked cores [M; L_b] (riding rows); 1 = the transposed
  * cores where they apply (default: >= 128 cores, basd_jacobi_plain4_fits(n), and -- with a gradient through the mixing
  * weights -- w_stack offered); 2 = the same for any batch; negative = keep.  Process-wide. */

@@ -15,7 +15,12 @@ the resize launch; parallel: Trainer(jpeg_decode="parallel"), the entropy stage 
 trainer's DevicePrefetcher; V is a depth, or DEPTH:lowest for a side stream of the lowest priority; 0, the default, is
 the serial path.  Several values: --windows windows of --steps steps for each, alternating in this one process, every
 window a host clock around a device synchronise; then the loss alone, timed with events while the side stream holds
-the input work of a batch and while it is idle.  Prints GPU_MAX_HW_QUEUES as found in the environment.)"""
+the input work of a batch and while it is idle.  Prints GPU_MAX_HW_QUEUES as found in the environment.)
+[--teacher-cache]  (resnet50 only: Trainer(teacher_cache=batch) and a batch that carries "index"; the warm steps fill
+the cache, then every --prefetch variant is timed twice per round of windows, "uncached" -- the option switched off for
+the window: the usual step, the yardstick -- and "cached", in turn in this one process.  "gained" is true only if every
+cached window lies below every uncached one.  Also: the loss alone through forward_cached, one store and one load
+between events, and the cache's bytes at this batch shape.)"""
 import argparse, os, sys, time
 from types import SimpleNamespace
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,6 +44,7 @@ ap.add_argument("--resize-crop", action="store_true")
 ap.add_argument("--jpeg-decode", nargs="?", const="serial", choices=("serial", "parallel"), default=None)
 ap.add_argument("--prefetch", nargs="+", default=["0"])
 ap.add_argument("--windows", type=int, default=1)
+ap.add_argument("--teacher-cache", action="store_true")
 args = ap.parse_args()
 
 
@@ -58,6 +64,8 @@ if args.resize_crop and not args.uint8:
     ap.error("--resize-crop needs --uint8")
 if args.jpeg_decode and not args.resize_crop:
     ap.error("--jpeg-decode needs --resize-crop")
+if args.teacher_cache and args.teacher != "resnet50":
+    ap.error("--teacher-cache needs a teacher with one extracted layer (--teacher resnet50)")
 files = None
 if args.resize_crop:
     # made before the GPU is opened (the pictures are encoded, and for --resize-crop decoded, with Pillow on the host)
@@ -82,7 +90,8 @@ tr = T.Trainer(student, cfg, teacher, student_info=SM.probe_model(student, 224),
                image_stats={"clean": ((0.5,) * 3, (0.25,) * 3), "augmented": ((0.5,) * 3, (0.25,) * 3)} if args.uint8 else None,
                mix_dtype=ac if args.uint8 else None, trivial_augment=args.trivial_augment,
                resize_crop=args.resize_crop,
-               jpeg_decode={None: False, "serial": True, "parallel": "parallel"}[args.jpeg_decode])
+               jpeg_decode={None: False, "serial": True, "parallel": "parallel"}[args.jpeg_decode],
+               teacher_cache=args.batch if args.teacher_cache else None)
 g = torch.Generator().manual_seed(1)
 B = args.batch
 # images with per-image structure (a random colour cast + noise) so that the teacher features are not pure noise
@@ -100,6 +109,8 @@ elif args.resize_crop:
     from basd_amd.jpeg import pillow_fallback
     from basd_amd.resize import pack_images
     step_batch = {"images": pack_images([pillow_fallback(f) for f in files]).pin_memory(), "label": batch["label"]}
+if args.teacher_cache:
+    step_batch = dict(step_batch, index=torch.randperm(B, generator=g))      # the "dataset" is this one batch
 
 
 def timed(fn, n):
@@ -117,10 +128,17 @@ prefetchers = {name: DevicePrefetcher(tr.prepare_batch, device=dev, depth=depth,
                for name, depth, priority in variants}
 
 
-def window(name):
+# with --teacher-cache every variant runs in two modes; "uncached" switches the option off for the window
+modes = ("uncached", "cached") if args.teacher_cache else (None,)
+cache = tr.teacher_cache                                    # the capacity, until the first step has built the cache
+label = lambda name, mode: name if mode is None else f"{name}/{mode}"
+
+
+def window(name, mode=None):
     """--steps steps through the trainer's prefetcher, as _train_epoch feeds them (its metrics code aside)."""
     global out
     tr._prefetcher = prefetchers[name]
+    tr.teacher_cache = cache if mode == "cached" else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for prepared in tr._prefetcher.iterate(feed):
@@ -130,16 +148,22 @@ def window(name):
 
 
 for name in prefetchers:                                   # warm-up: every variant once (its stream, its events)
-    tr._prefetcher = prefetchers[name]
-    for prepared in tr._prefetcher.iterate(feed[:2]):
-        out = tr.step_prepared(prepared)
-windows = {name: [] for name in prefetchers}
-losses = {name: [] for name in prefetchers}                # the last step's loss of every window
+    for mode in modes:                                     # (cached: the first step misses and fills, the second hits)
+        tr._prefetcher = prefetchers[name]
+        tr.teacher_cache = cache if mode == "cached" else None
+        for prepared in tr._prefetcher.iterate(feed[:2]):
+            out = tr.step_prepared(prepared)
+        if mode == "cached":
+            cache = tr.teacher_cache
+windows = {label(name, mode): [] for name in prefetchers for mode in modes}
+losses = {key: [] for key in windows}                      # the last step's loss of every window
 for _ in range(args.windows):
     for name in prefetchers:
-        windows[name].append(round(window(name), 2))
-        losses[name].append(round(float(out["loss"]), 4))
-step_ms = sum(windows[variants[0][0]]) / args.windows
+        for mode in modes:
+            windows[label(name, mode)].append(round(window(name, mode), 2))
+            losses[label(name, mode)].append(round(float(out["loss"]), 4))
+tr.teacher_cache = None
+step_ms = sum(windows[label(variants[0][0], modes[0])]) / args.windows
 acx = torch.autocast("cuda", dtype=ac, enabled=ac is not None)
 
 
@@ -193,10 +217,45 @@ loss_events = {"side_idle": loss_by_events(None)}
 for name, pf in prefetchers.items():
     if pf.stream is not None:
         loss_events[f"side_busy[{name}]"] = loss_by_events(pf.stream)
+cache_report = None
+if args.teacher_cache:
+    from basd_amd.ops import TeacherSide
+    loss_only()
+    side = TeacherSide(*(t.clone() for t in tr.basd_loss.last_teacher_side()))
+    index_host = step_batch["index"]
+    index_dev = index_host.to(dev)
+
+    def loss_cached():
+        loss = tr.basd_loss.forward_cached(lg, batch["label"], s_leaf, cache.load(index_host, device_index=index_dev))
+        loss.backward()
+
+    def by_events(fn):
+        pairs = []
+        torch.cuda.synchronize()
+        for _ in range(args.steps):
+            pairs.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+            pairs[-1][0].record()
+            fn()
+            pairs[-1][1].record()
+        torch.cuda.synchronize()
+        return round(sum(a.elapsed_time(b) for a, b in pairs) / args.steps, 4)
+
+    loss_cached()
+    cache_report = {
+        "loss_fwd_bwd_cached_ms": round(timed(loss_cached, args.steps), 2),
+        "loss_fwd_bwd_cached_ms_by_events": by_events(loss_cached),
+        "store_ms_by_events": by_events(lambda: cache.store(index_host, side, device_index=index_dev)),
+        "load_ms_by_events": by_events(lambda: cache.load(index_host, device_index=index_dev).tensors()),
+        "n": cache.n, "n_s": cache.n_s, "capacity": cache.capacity, "nbytes": cache.nbytes,
+        "record_bytes": cache.record_bytes(cache.n, cache.n_s),
+        "mean_ms": {key: round(sum(v) / len(v), 2) for key, v in windows.items()},
+        # every cached window below every uncached one, per variant
+        "gained": {name: max(windows[f"{name}/cached"]) < min(windows[f"{name}/uncached"]) for name in prefetchers}}
 print({"batch": B, "dtype": args.dtype, "optimizer": args.optimizer, "mixup": args.mixup, "teacher": args.teacher,
        "attn_capture": args.attn_capture, "uint8": args.uint8, "trivial_augment": args.trivial_augment, "resize_crop": args.resize_crop,
        "jpeg_decode": args.jpeg_decode, "prefetch": args.prefetch, "steps": args.steps, "step_ms": round(step_ms, 2),
        "step_ms_windows": windows, "loss_windows": losses, "images_per_s": round(B / step_ms * 1e3, 1),
        "student_fwd_nograd_ms": round(s_ms, 2), "teacher_fwd_ms": round(t_ms, 2), "loss_fwd_bwd_ms": round(l_ms, 2),
        "loss_fwd_bwd_ms_by_events": loss_events, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "unset"),
-       "loss_share": round(l_ms / step_ms, 3), "loss": float(out["loss"]), "ranks": dict(tr.basd_loss.layer_selector.subspace_ranks)})
+       "loss_share": round(l_ms / step_ms, 3), "loss": float(out["loss"]), "ranks": dict(tr.basd_loss.layer_selector.subspace_ranks),
+       **({"teacher_cache": cache_report} if cache_report is not None else {})})

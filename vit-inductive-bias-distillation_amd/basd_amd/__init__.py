@@ -23,6 +23,8 @@ Sub-modules:
   ``png``      ``PngDecoder`` / ``pack_pngs`` / ``collate_png`` / ``parse_png``: Pillow-exact 8-bit PNG decoding of a batch of
                files' bytes into a ragged batch, two launches per batch
   ``prefetch``  ``DevicePrefetcher``: the input work of the next batch on a side stream while the step runs
+  ``teacher_cache``  ``TeacherCache``: the teacher side of a single-layer teacher per dataset image on the device, one
+               scatter and one gather launch (``BASDLoss.forward_cached``, ``Trainer(teacher_cache=...)``)
   ``_launch``  what those one-launch stages share on the host: argument checks, dtype codes, the record-table uploader
   ``synth``    seeded synthetic feature stacks (benchmark + tests)
 """

@@ -85,6 +85,10 @@ SIGNATURES = {
                                 f32, vp, vp],
     "basd_procrustes_forward_fused": [vp, vp],
     "basd_procrustes_plan_query": [vp, vp],
+    "basd_procrustes_forward_cached": [vp, vp],
+    "basd_procrustes_plan_query_cached": [vp, vp],
+    "basd_teacher_cache_store": [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp],
+    "basd_teacher_cache_load": [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp],
     "basd_procrustes_tuning": [i32],
     "basd_jacobi_plain4_fits": [i32],
     "basd_stack_product_t": [vp, vp, i64, i32, i32, i32, vp, i64, vp],

@@ -334,11 +334,27 @@ class _SingleTeacherTotal(torch.autograd.Function):
     """(ce, has_cls, zero_param, teachers, attns, *students) -> (total, geo_layers): the Procrustes loss of every
     extraction layer against ONE teacher layer (mixing weights exactly 1) and its UW-SO combination with the base
     loss, as a single autograd node.  The student gradients for a unit upstream gradient are queued by forward
-    (see ``_ProcrustesLayers``); backward is one small product for the weights and one scaling per layer."""
+    (see ``_ProcrustesLayers``); backward is one small product for the weights and one scaling per layer.
+
+    ``attns is None``: ``teachers`` is the teacher SIDE (``ops.TeacherSide`` or what ``TeacherCache.load`` returns) and
+    the call is ``ops.procrustes_forward_cached``; nothing else differs.  ``last_side``: the teacher side the most
+    recent forward's call read (``BASDLoss.last_teacher_side``)."""
+
+    last_side = None
 
     @staticmethod
     def forward(ctx, ce, has_cls, zero_param, teachers, attns, *students):
         E = len(students)
+
+        def procrustes(**kw):
+            if attns is None:
+                kw.pop("need_mix_grad")
+                pc = ops.procrustes_forward_cached(list(students), teachers, **kw)
+            else:
+                pc = ops.procrustes_forward(list(students), teachers, attns, ones.view(-1, 1), has_cls, **kw)
+            _SingleTeacherTotal.last_side = pc.teacher_side
+            return pc
+
         need_bwd = any(s.requires_grad for s in students)
         ctx.n_students = E
         ctx.dtypes = [s.dtype for s in students]
@@ -349,8 +365,7 @@ class _SingleTeacherTotal(torch.autograd.Function):
         # no dozen torch micro-kernels for the weights between the Procrustes kernels and the rank read-back)
         ctx.final = need_bwd and ce.dtype == torch.float32 and ce.numel() == 1 and ce.is_cuda
         if ctx.final:
-            pc = ops.procrustes_forward(list(students), teachers, attns, ones.view(-1, 1), has_cls, need_backward=True,
-                                        need_mix_grad=False, uwso_ce=ce.detach().reshape(1))
+            pc = procrustes(need_backward=True, need_mix_grad=False, uwso_ce=ce.detach().reshape(1))
             uw = pc.uw
             geo_layers = uw[4 + E:4 + 2 * E]
             ctx.unit_grads = pc.dx      # (E, B, N_s, D_s): d total / d student tokens for a unit upstream gradient
@@ -358,8 +373,7 @@ class _SingleTeacherTotal(torch.autograd.Function):
             ctx.save_for_backward(uw[:2])
             ctx.mark_non_differentiable(geo_layers)
             return uw[2].reshape(()), geo_layers
-        pc = ops.procrustes_forward(list(students), teachers, attns, ones.view(-1, 1), has_cls, need_backward=need_bwd,
-                                    need_mix_grad=False, grad_layers=ones if need_bwd else None)
+        pc = procrustes(need_backward=need_bwd, need_mix_grad=False, grad_layers=ones if need_bwd else None)
         geo_layers = pc.loss_b.mean(dim=1)
         ctx.unit_grads = pc.dx          # (E, B, N_s, D_s): gradients for a unit upstream gradient, one buffer
         # UW-SO (combined.py:78-85) on the detached values
@@ -1151,6 +1165,14 @@ class GrassmannianLayerSelector(nn.Module):
 # --------------------------------------------------------------------------- #
 # reference src/losses/combined.py:17-85
 # --------------------------------------------------------------------------- #
+# why a step has no teacher side to cache (``BASDLoss.last_teacher_side`` / ``forward_cached``)
+_MULTI_LAYER_TEACHER = ("the teacher side can only be cached for ONE teacher layer: with L > 1 the mixing weights depend "
+                        "on the student (layer_selector.py:99-112), so the mixed teacher's Gram is not a property of the "
+                        "image")
+_TEACHER_REQUIRES_GRAD = ("the teacher side can only be cached for a frozen teacher: a teacher tensor requires grad, and "
+                          "a cached step has no path back to it")
+
+
 class BASDLoss(nn.Module):
     def __init__(
         self,
@@ -1181,6 +1203,7 @@ class BASDLoss(nn.Module):
             teacher_dim=teacher_dim,
         )
         self.last_components: dict[str, torch.Tensor] = {}
+        self._last_side = None       # ``last_teacher_side``: the last step's teacher side, or why it has none (str)
         self._side_streams: dict = {}
         # The reference reads the ranks (and raises on rank 0) inside forward; so do we -- but with one teacher layer the
         # ranks do not feed the loss, and waiting for them is waiting for the whole factorisation (~1.5 ms).
@@ -1491,6 +1514,12 @@ class BASDLoss(nn.Module):
                 comp["tridiag_check"] = sel.last_check
         comp.update(ce=ce_loss.detach(), geo_layers=geo_layers.detach(), mix=mix.detach())
         self.last_components = comp
+        if len(keys) != 1:
+            self._last_side = _MULTI_LAYER_TEACHER
+        elif any(t.requires_grad for t in (*teachers, *attns)):
+            self._last_side = _TEACHER_REQUIRES_GRAD
+        else:
+            self._last_side = _SingleTeacherTotal.last_side
         ops.trace("combine_queued")
         if selector_tail is not None:
             if self.sync_ranks:
@@ -1508,5 +1537,63 @@ class BASDLoss(nn.Module):
                 previous, sel._pending_tail = sel._pending_tail, selector_tail
                 if previous is not None:
                     previous()
+        ops.trace("fwd_out")
+        return total
+
+    def last_teacher_side(self) -> "ops.TeacherSide":
+        """All that the most recent ``forward`` (or ``forward_cached``) read of its ONE teacher layer: ``ops.TeacherSide``
+        (``g``, ``omega``, ``omega_t``).  ``g`` and ``omega_t`` are views of the Procrustes call's persistent scratch:
+        valid only until the next Procrustes call on that stream, so hand them to ``TeacherCache.store`` right behind
+        the forward.  ``ValueError`` after a multi-layer forward, or when a teacher tensor required grad."""
+        side = self._last_side
+        if side is None:
+            raise RuntimeError("last_teacher_side: no forward has run yet")
+        if isinstance(side, str):
+            raise ValueError(side)
+        return side
+
+    def forward_cached(self, student_output: torch.Tensor, targets: torch.Tensor,
+                       student_intermediates: dict[int, torch.Tensor], teacher_side) -> torch.Tensor:
+        """``forward`` for ONE teacher layer without the teacher: ``teacher_side`` is what ``last_teacher_side()`` gave
+        after a ``forward`` on the same teacher inputs (an ``ops.TeacherSide``), usually by way of ``TeacherCache.store``
+        / ``load``.  The base loss and the same autograd node as ``forward`` (the UW-SO combination inside the call
+        where ``forward`` takes it) on ``ops.procrustes_forward_cached``: ``total``, ``geo_layers`` and the student
+        gradients have the bits of ``forward``.  ``last_components`` gets ``ce``, ``geo_layers`` and ``mix`` (ones).  A
+        read-back that a previous uncached step deferred is completed first (``finish_pending``).
+
+        What a cached step does NOT do -- the price of the option; at one teacher layer nothing of the loss value
+        depends on it: the selector does not run, so ``layer_selector.subspace_ranks`` keeps its last values,
+        ``last_components`` has no ``d_grass_sq``, and the reference's rank-0 ``LinAlgError`` is not raised.
+
+        ``ValueError`` for more than one teacher layer's side (with L > 1 the mixing weights depend on the student, so
+        the mixed teacher's Gram is not a property of the image) and for a teacher side that requires grad."""
+        ops.trace("fwd_in")
+        if isinstance(teacher_side, dict):
+            teacher_side = [teacher_side[k] for k in sorted(teacher_side)]
+        if isinstance(teacher_side, (list, tuple)) and not all(isinstance(t, torch.Tensor) for t in teacher_side):
+            if len(teacher_side) != 1:          # a collection of sides, one per teacher layer
+                raise ValueError(_MULTI_LAYER_TEACHER)
+            teacher_side = teacher_side[0]
+        if not hasattr(teacher_side, "into"):
+            if len(teacher_side) != 3:
+                raise ValueError(f"a teacher side is (g, omega, omega_t); got {len(teacher_side)} tensors")
+            teacher_side = ops.TeacherSide(*teacher_side)
+            if teacher_side.g.dim() != 3:
+                raise ValueError(_MULTI_LAYER_TEACHER)
+            if any(t.requires_grad for t in teacher_side):
+                raise ValueError(_TEACHER_REQUIRES_GRAD)
+        students = [student_intermediates[l] for l in self.token_layers]
+        for s in students:
+            if s.shape[1] != self.num_student_tokens:
+                raise RuntimeError(
+                    f"student tokens have {s.shape[1]} tokens, expected num_student_tokens={self.num_student_tokens}")
+        sel = self.layer_selector
+        sel.finish_pending()
+        ce_loss = _base_loss(self.base_criterion, student_output, targets)
+        mix = ops._device_consts((1.0,) * len(students), torch.float32, students[0].device).view(-1, 1)
+        total, geo_layers = _SingleTeacherTotal.apply(ce_loss, bool(self.teacher_has_cls_token), sel.log_temperatures,
+                                                      teacher_side, None, *students)
+        self.last_components = dict(ce=ce_loss.detach(), geo_layers=geo_layers.detach(), mix=mix.detach())
+        self._last_side = _SingleTeacherTotal.last_side
         ops.trace("fwd_out")
         return total

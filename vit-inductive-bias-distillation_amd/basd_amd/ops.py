@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from functools import lru_cache
+from typing import NamedTuple
 
 import torch
 
@@ -683,6 +684,21 @@ class ProcrustesContext:
     mixgrad: dict | None = None   # extra state kept only when the mixing weights need a gradient
     dx: torch.Tensor | None = None   # (E, B, n_s, D_s) student gradients queued with the forward (``grad_layers``)
     uw: torch.Tensor | None = None   # (4 + 2 E,) UW-SO combination computed inside the call (``uwso_ce``)
+    # one teacher layer only: all the call read of the teacher.  ``g`` and ``omega_t`` are VIEWS of the plan's scratch,
+    # valid only until the next Procrustes call on that stream (see ``TeacherSide``)
+    teacher_side: "TeacherSide | None" = None
+
+
+class TeacherSide(NamedTuple):
+    """What a Procrustes call with ONE teacher layer (mixing weight exactly 1, layer_selector.py:110-112) reads of the
+    teacher (relational.py:22-39): ``g`` (B, n, n) fp64, the Gram of the centred, weighted teacher tokens on the core
+    grid; ``omega`` (B, n_s) and ``omega_t`` (B, n) fp32, the token weights on the student's and on the core grid.  A
+    function of the teacher's input alone.  As ``ProcrustesContext.teacher_side`` the first and the last are views of
+    the call's persistent scratch: valid only until the next Procrustes call on that stream -- copy them
+    (``TeacherCache.store``) before that."""
+    g: torch.Tensor
+    omega: torch.Tensor
+    omega_t: torch.Tensor
 
 
 def _check_common_layout(tensors: list[torch.Tensor], what: str) -> list[torch.Tensor]:
@@ -716,14 +732,18 @@ class _ProcrustesPlan:
         """The C planner's routes for ``self.args`` under the hooks as they stand (no HIP call)."""
         import ctypes
         out = (ctypes.c_long * len(self.ROUTE_FIELDS))()
-        status = _lib.query("basd_procrustes_plan_query", ctypes.addressof(self.args), ctypes.cast(out, ctypes.c_void_p))
+        name = "basd_procrustes_plan_query_cached" if self.given else "basd_procrustes_plan_query"
+        status = _lib.query(name, ctypes.addressof(self.args), ctypes.cast(out, ctypes.c_void_p))
         if status != 0:
-            raise RuntimeError(f"basd_procrustes_plan_query failed with status {status} (invalid argument / unsupported shape)")
+            raise RuntimeError(f"{name} failed with status {status} (invalid argument / unsupported shape)")
         return dict(zip(self.ROUTE_FIELDS, out))
 
     def __init__(self, E, L, B, n_s, d_s, n_t, d_t, H, A, has_cls, need_bwd, need_mix_grad, want_sweeps, want_dx,
-                 want_uw, s_layout, t_layout, dev):
+                 want_uw, s_layout, t_layout, dev, given=False):
         import ctypes
+        # given: the plan of ``procrustes_forward_cached`` -- the teacher side is an input, so the teacher-side scratch
+        # (tc, mu_t, the split Gram's slabs) is not allocated and the cached planner is the one asked
+        self.given = given
         self.E, self.L, self.B, self.n_s, self.d_s, self.n_t, self.d_t = E, L, B, n_s, d_s, n_t, d_t
         n_a = A - (1 if has_cls else 0)
         n = min(n_s, n_t)
@@ -743,13 +763,13 @@ class _ProcrustesPlan:
         self.kept_total = sum(self.kept_padded)
         # ---- scratch
         g_splits = 1
-        if GB < 1024 and d_t >= 512:           # few teacher Grams with a long feature axis: split the contraction
+        if not given and GB < 1024 and d_t >= 512:           # few teacher Grams with a long feature axis: split the contraction
             g_splits = max(1, min(1024 // GB, d_t // 256, 16))
         self.g_splits = g_splits
         self.g_all = torch.empty((EB + GB + (g_splits * GB if g_splits > 1 else 0), n, n), device=dev, dtype=torch.float64)
         self.l_all = torch.empty((EB + GB, n, n), device=dev, dtype=torch.float64)
         self.W = torch.empty((EB, n, 2 * n), **f32)        # memory == column-major (2n x n)
-        self.tc = torch.empty((G, B, n, d_t), **f32)
+        self.tc = torch.empty((0,) if given else (G, B, n, d_t), **f32)
         self.ints = torch.empty((_lib.query("basd_jacobi_workspace_ints", EB, MAX_SWEEPS) + EB,), device=dev,
                                 dtype=torch.int32)
         self.sweeps = self.ints[-EB:] if want_sweeps else None
@@ -793,7 +813,7 @@ class _ProcrustesPlan:
         # the transposed route (cores the plain LDS solver holds), it is rebuilt into this buffer
         self.w_stack = torch.empty((EB, n, 2 * n), **f32) if route["rebuild_usigma"] else None
         self.sigma_u = torch.empty((EB, n), **f32) if route["rebuild_usigma"] else None
-        sizes = [GB * n, GB * d_t, route["tr_part_floats"], EB * n]
+        sizes = [GB * n, 0 if given else GB * d_t, route["tr_part_floats"], EB * n]
         padded = [(c + 63) // 64 * 64 for c in sizes]
         self.omega_t, self.mu_t, self.tr_part, self.sigma = (
             piece[:c] for piece, c in zip(torch.split(torch.empty((sum(padded),), **f32), padded), sizes))
@@ -910,8 +930,102 @@ def procrustes_forward(students: list[torch.Tensor], teachers: list[torch.Tensor
                        has_cls=has_cls, n_a=n_a, n=n, n_s=n_s, gather=plan.gt, student_taps=plan.tp, attn_taps=plan.atp,
                        route=plan.route)
     sweeps = plan.sweeps.clone() if plan.sweeps is not None else None
+    side = TeacherSide(plan.g_all[EB:EB + B], omega[0], plan.omega_t.view(B, n)) if L == 1 else None
     return ProcrustesContext(omega, mu_s, a_prime, k_prime, terms[0], terms[1], terms[2], terms[3], sweeps, mixgrad,
-                             dx, uw)
+                             dx, uw, side)
+
+
+def procrustes_forward_cached(students: list[torch.Tensor], teacher_side, *, need_backward: bool = True,
+                              want_sweeps: bool = False, grad_layers: torch.Tensor | None = None,
+                              uwso_ce: torch.Tensor | None = None) -> ProcrustesContext:
+    """``procrustes_forward`` for ONE teacher layer with the teacher side GIVEN instead of computed
+    (basd_procrustes_forward_cached): no teacher tokens, no attention, no mixing weights (exactly 1).
+    ``teacher_side``: a ``TeacherSide`` of tensors (copied into the call's slots), or what ``TeacherCache.load`` returns
+    (gathered straight into them by one launch).  The token weights, the centring and the teacher Gram are not queued;
+    everything from the student projection on is the uncached call's, through the same ``_ProcrustesPlan`` cache and
+    allocation scheme, so with the teacher side of an uncached call on the same students every output has that call's
+    bits.  The returned context's ``teacher_side`` is the one the call read (views, as in ``procrustes_forward``)."""
+    import ctypes
+    E = len(students)
+    students = [as_supported(s) for s in students]
+    students = _check_common_layout([s if s.stride(2) == 1 else s.contiguous() for s in students],
+                                    "student token tensors")
+    _require_cuda(*students)
+    s0 = students[0]
+    dev = s0.device
+    B, n_s, d_s = s0.shape
+    gather = getattr(teacher_side, "into", None)
+    if gather is not None:
+        n = teacher_side.n
+        fits = (teacher_side.B, teacher_side.n_s) == (B, n_s) and n <= n_s
+        got = f"{teacher_side.B} cached rows of n={n}, n_s={teacher_side.n_s}"
+    else:
+        shapes = [tuple(t.shape) for t in teacher_side]
+        n = shapes[0][-1]
+        fits = shapes == [(B, n, n), (B, n_s), (B, n)] and n <= n_s
+        got = f"g {shapes[0]}, omega {shapes[1]}, omega_t {shapes[2]}"
+    if not fits:
+        raise ValueError(f"teacher side ({got}) does not fit student tokens {tuple(s0.shape)}: expected g (B, n, n), "
+                         "omega (B, n_s), omega_t (B, n) with n <= n_s")
+    if gather is None:
+        _require_cuda(*teacher_side)
+        if (teacher_side.g.dtype, teacher_side.omega.dtype, teacher_side.omega_t.dtype) != \
+                (torch.float64, torch.float32, torch.float32):
+            raise TypeError("teacher side must be (fp64 g, fp32 omega, fp32 omega_t)")
+    need_bwd = need_backward or grad_layers is not None
+    want_dx = grad_layers is not None or uwso_ce is not None
+    stream = _stream()
+    s_layout = (_dtype_code(s0), s0.stride(0), s0.stride(1), int(all(s.data_ptr() % 16 == 0 for s in students)))
+    # the teacher's own token grid and width do not matter any more: the core grid stands for the first (it decides
+    # the student-side taps exactly as n_t < n_s does), 1 for the second
+    key = ("given", E, B, n_s, d_s, n, need_bwd, want_sweeps, want_dx, uwso_ce is not None, dev, stream, TWO_PASS_SVD,
+           s_layout)
+    plan = _PROCRUSTES_PLANS.get(key)
+    if plan is None:
+        plan = _ProcrustesPlan(E, 1, B, n_s, d_s, n, 1, 1, n_s, False, need_bwd, False, want_sweeps, want_dx,
+                               uwso_ce is not None, s_layout, (0, 0, 0, 1), dev, given=True)
+        if len(_PROCRUSTES_PLANS) >= 8:
+            torch.cuda.synchronize(dev)
+            _PROCRUSTES_PLANS.clear()
+        _PROCRUSTES_PLANS[key] = plan
+    EB = E * B
+    kept = torch.empty((plan.kept_total,), device=dev, dtype=torch.float32)
+    omega, mu_s, a_prime, k_prime, terms, uw = (piece[:c] for piece, c in
+                                                zip(torch.split(kept, plan.kept_padded), plan.kept_sizes))
+    omega, mu_s = omega.view(1, B, n_s), mu_s.view(E, B, d_s)
+    a_prime = a_prime.view(E, B, n, d_s)
+    k_prime = k_prime.view(E, B, n, n) if need_bwd else None
+    terms = terms.view(4, E, B)
+    uw = uw if uwso_ce is not None else None
+    dx = torch.empty((E, B, n_s, d_s), device=dev, dtype=torch.float32) if want_dx else None
+    if plan.sweeps is not None:
+        plan.sweeps.zero_()
+    if uwso_ce is not None:
+        assert uwso_ce.dtype == torch.float32 and uwso_ce.numel() == 1 and uwso_ce.device == dev
+    if grad_layers is not None:
+        grad_layers = grad_layers.contiguous().float()
+    side = TeacherSide(plan.g_all[EB:EB + B], omega[0], plan.omega_t.view(B, n))
+    if gather is not None:
+        gather(*side)
+    else:
+        for dst, src in zip(side, teacher_side):
+            dst.copy_(src)
+
+    args = plan.args
+    for e, s in enumerate(students):
+        plan.host_ptrs[e] = s.data_ptr()
+    args.student_ptrs = _ptr_table(students).data_ptr()
+    args.omega, args.mu_s = omega.data_ptr(), mu_s.data_ptr()
+    args.tr_s, args.tr_t, args.nuc, args.loss_b = (terms[i].data_ptr() for i in range(4))
+    args.a_prime, args.k_prime = a_prime.data_ptr(), _ptr(k_prime)
+    args.dx, args.grad_layers = _ptr(dx), _ptr(grad_layers)
+    args.uw_ce, args.uw_out = _ptr(uwso_ce), _ptr(uw)
+    gpu_mark("procrustes_begin")
+    _lib.call("basd_procrustes_forward_cached", ctypes.addressof(args), stream)
+    gpu_mark("procrustes_end")
+    sweeps = plan.sweeps.clone() if plan.sweeps is not None else None
+    return ProcrustesContext(omega, mu_s, a_prime, k_prime, terms[0], terms[1], terms[2], terms[3], sweeps, None,
+                             dx, uw, side)
 
 
 def scale_unless_one(x: torch.Tensor, num: torch.Tensor, den: torch.Tensor | None = None) -> None:

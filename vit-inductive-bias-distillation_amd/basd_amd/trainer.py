@@ -130,18 +130,43 @@ class Trainer:
     prepares bit-identical batches with and without it; the one exception is a model that itself draws from the CPU
     generator in its forward (dropout in a CPU model): its draws fall between other batches' draws.  A model on the GPU
     draws from the device generator and is unaffected.  While an epoch or a validation runs, the stage objects of this
-    trainer belong to its prefetcher: nothing else may call them."""
+    trainer belong to its prefetcher: nothing else may call them.
+    ``teacher_cache``: ``None``, a ``basd_amd.teacher_cache.TeacherCache`` or an int (a capacity in images -- the dataset's
+    length; the cache is then built from the first batch's shapes).  GPU only, and only for a teacher whose
+    ``extract_intermediates`` returns ONE layer (``feature_format != "token"``: every CNN teacher); any other raises
+    ``ValueError`` here.  Batches must carry ``"index"``: the ``(B,)`` int64 dataset indices of their images (the dataset's
+    transform returns ``{..., "index": i}``; ``default_collate``, ``collate_ragged``, ``collate_jpeg`` and ``collate_png``
+    pass the key through); a batch without it raises ``KeyError``.  ``prepare_batch`` asks the cache on the host whether
+    every image of the batch has been seen (``"teacher_cached"`` in what it returns); if so it makes no clean view and the
+    step runs neither the teacher nor the teacher side of the loss (``BASDLoss.forward_cached``, which see for what such
+    a step leaves out: the selector, hence ``subspace_ranks`` and ``d_grass_sq``); if not, the step is the usual one and
+    its teacher side is stored behind the loss's forward.  Loss and gradients have the same bits either way; the draws
+    and their order do not change (the clean view draws nothing).  The cache is valid for one teacher, one clean
+    transform, one set of clean statistics and one autocast dtype, and never invalidates itself (``TeacherCache``);
+    ``evaluate`` does not use it and checkpoints do not contain it.  With more than one rank each rank fills what its
+    sampler shows it."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
                  resize_crop: bool = False, jpeg_decode=False, png_decode: bool = False, max_grad_norm=None,
                  skip_nonfinite: bool = False, prefetch: int = 0, resize_interpolation="bilinear",
-                 check_factorisations: bool = False) -> None:
+                 check_factorisations: bool = False, teacher_cache=None) -> None:
         if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
             raise ValueError(f"prefetch must be an int >= 0 (got {prefetch!r})")
         self._guarded = max_grad_norm is not None or bool(skip_nonfinite)
         self._skipped_seen = 0
+        if teacher_cache is not None:
+            from .teacher_cache import TeacherCache
+            if not isinstance(teacher_cache, TeacherCache) and (
+                    isinstance(teacher_cache, bool) or not isinstance(teacher_cache, int) or teacher_cache <= 0):
+                raise ValueError(f"teacher_cache must be None, a TeacherCache or a capacity > 0 (got {teacher_cache!r})")
+            if teacher.feature_format == "token":
+                raise ValueError("teacher_cache needs a teacher with ONE extracted layer (feature_format != 'token'): a "
+                                 "token-format teacher hands over every block, and with more than one teacher layer "
+                                 "the mixing weights depend on the student, so the mixed teacher's Gram is not a "
+                                 f"property of the image; got feature_format={teacher.feature_format!r}")
+        self.teacher_cache = teacher_cache
         if self._guarded and optimizer != "schedulefree":
             raise ValueError("max_grad_norm and skip_nonfinite are part of AdamWScheduleFree's update: they need "
                              f"optimizer='schedulefree'; got optimizer={optimizer!r}")
@@ -261,12 +286,14 @@ class Trainer:
                         f"{'given' if self.image_stats is not None else None}{got}")
 
     # -- one batch: the body of the reference's _train_epoch loop (trainer.py:133-164)
-    def prepare_views(self, batch: dict):
+    def prepare_views(self, batch: dict, *, want_clean: bool = True):
         """``(clean, augmented)`` of a batch on the device.  With ``resize_crop`` both are made from the batch's
-        ``"images"`` by one launch (uint8, ``(B, C, S, S)``); without, they are the batch's own entries."""
+        ``"images"`` by one launch (uint8, ``(B, C, S, S)``); without, they are the batch's own entries.
+        ``want_clean=False`` (the teacher side of every image is cached): ``clean`` is ``None``, not uploaded or made."""
         dev = self.device
         if self._resizer is None:
-            return batch["clean"].to(dev, non_blocking=True), batch["augmented"].to(dev, non_blocking=True)
+            clean = batch["clean"].to(dev, non_blocking=True) if want_clean else None
+            return clean, batch["augmented"].to(dev, non_blocking=True)
         from .resize import RaggedBatch
         images = batch.get("images")
         if self._decoder is not None:
@@ -280,19 +307,36 @@ class Trainer:
         if not isinstance(images, RaggedBatch):
             raise TypeError("resize_crop works on decoded images (the loader decodes, nothing else): the batch needs "
                             f"'images', a RaggedBatch (collate_fn=collate_ragged); got {sorted(batch)}")
+        if not want_clean:
+            views = self._resizer(images.to(dev, non_blocking=True), batch.get("crop_params"), views=("augmented",))
+            return None, views["augmented"]
         views = self._resizer(images.to(dev, non_blocking=True), batch.get("crop_params"))
         return views["clean"], views["augmented"]
+
+    def _batch_index(self, batch: dict) -> torch.Tensor:
+        """The batch's ``"index"`` as a host int64 vector (``teacher_cache``)."""
+        if "index" not in batch:
+            raise KeyError("'index': teacher_cache needs the dataset indices of the batch's images, a (B,) int64 tensor "
+                           f"under 'index' (the dataset's transform returns {{..., 'index': i}}); got {sorted(batch)}")
+        return torch.as_tensor(batch["index"]).to("cpu", torch.int64).reshape(-1)
 
     def prepare_batch(self, batch: dict) -> dict:
         """The input half of a step, everything ahead of the model forwards: the transfer, the views, the augmentation
         and the mixing, with the checks that raise ``TypeError``.  Returns ``clean``, ``augmented``, ``targets`` and
         ``mixed_targets`` on the device.  It draws crop, augment and mix, in that order, on the global CPU generator and
-        touches neither model, so it may run ahead of the step before it (``prefetch``)."""
+        touches neither model, so it may run ahead of the step before it (``prefetch``).  With ``teacher_cache`` also
+        ``index`` (on the device), ``index_host`` and ``teacher_cached``, decided here on the host from the rows whose
+        store has been queued; when it is true there is no ``clean``."""
         dev = self.device
-        clean, student_imgs = self.prepare_views(batch)
+        index = None
+        cached = False
+        if self.teacher_cache is not None:
+            index = self._batch_index(batch)
+            cached = not isinstance(self.teacher_cache, int) and self.teacher_cache.has(index)
+        clean, student_imgs = self.prepare_views(batch, want_clean=not cached)
         targets = batch["label"].to(dev, non_blocking=True)
         mixed_targets = targets
-        if clean.dtype == torch.uint8 or student_imgs.dtype == torch.uint8:
+        if (clean is not None and clean.dtype == torch.uint8) or student_imgs.dtype == torch.uint8:
             self._require_fused("uint8 batches need", "the conversion and the normalisation are part of the fused launch",
                                 TypeError, clean=clean, augmented=student_imgs)
         if self._augmenter is not None:
@@ -302,26 +346,45 @@ class Trainer:
             student_imgs = self._augmenter(student_imgs, batch.get("augment_params"))
         if self.mixup == "fused":
             from .augment import MixParams
-            if clean.dtype == torch.uint8:
+            if clean is not None and clean.dtype == torch.uint8:
                 clean, _ = self._clean_mixer(clean, None, MixParams("none"))
             student_imgs, mixed_targets = self._mixer(student_imgs, targets)
         elif self.mixup:
             student_imgs, mixed_targets = mixup_cutmix(student_imgs, targets, self.config.model.num_classes)
-        return {"clean": clean, "augmented": student_imgs, "targets": targets, "mixed_targets": mixed_targets}
+        prepared = {"augmented": student_imgs, "targets": targets, "mixed_targets": mixed_targets}
+        if clean is not None:
+            prepared["clean"] = clean
+        if index is not None:
+            if index.numel() != targets.shape[0]:
+                raise ValueError(f"'index' has {index.numel()} entries for a batch of {targets.shape[0]}")
+            prepared.update(index=index.to(dev, non_blocking=True), index_host=index, teacher_cached=cached)
+        return prepared
 
     def step_prepared(self, prepared: dict) -> dict:
         """The rest of the step on what ``prepare_batch`` returned: both forwards, the loss, the backward, the update."""
         dev = self.device
-        clean, student_imgs = prepared["clean"], prepared["augmented"]
+        student_imgs = prepared["augmented"]
         targets, mixed_targets = prepared["targets"], prepared["mixed_targets"]
+        cached = prepared.get("teacher_cached", False)
         ac = torch.autocast(dev.type, dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None)
         with ac:
             logits, s_tokens = capture._extract_student(self.model, student_imgs, self.basd_loss.token_layers,
                                                         layer_paths=self._student_layer_paths,
                                                         has_cls_token=self._student_has_cls)
-            teacher_tokens, teacher_attns = capture.extract_intermediates(self._teacher, clean, attn=self.attn_capture)
+            if not cached:
+                teacher_tokens, teacher_attns = capture.extract_intermediates(self._teacher, prepared["clean"],
+                                                                              attn=self.attn_capture)
         # the loss is computed outside autocast: fp32 logits, tokens consumed in their own dtype (fp32 internal)
-        loss = self.basd_loss(logits.float(), mixed_targets, s_tokens, teacher_tokens, teacher_attns)
+        if cached:
+            # the gather is queued HERE, on the step's stream, not where the batch was prepared: it reads rows that
+            # stores on this stream wrote
+            side = self.teacher_cache.load(prepared["index_host"], device_index=prepared["index"])
+            loss = self.basd_loss.forward_cached(logits.float(), mixed_targets, s_tokens, side)
+        else:
+            loss = self.basd_loss(logits.float(), mixed_targets, s_tokens, teacher_tokens, teacher_attns)
+            if self.teacher_cache is not None:
+                # right behind the forward, ahead of the backward: the teacher side is a view of the call's scratch
+                self._store_teacher_side(prepared)
         loss.backward()
         if getattr(self.optimizer, "zero_grad_in_step", False):
             # schedule-free AdamW over the flat bucket: 1 / world (where the backend only sums) and the zeroing of the
@@ -335,6 +398,13 @@ class Trainer:
         if self._guarded:
             out["grad_norm"] = self.optimizer.last_grad_norm()
         return out
+
+    def _store_teacher_side(self, prepared: dict) -> None:
+        side = self.basd_loss.last_teacher_side()
+        if isinstance(self.teacher_cache, int):
+            from .teacher_cache import TeacherCache
+            self.teacher_cache = TeacherCache(self.teacher_cache, side.g.shape[-1], side.omega.shape[-1], self.device)
+        self.teacher_cache.store(prepared["index_host"], side, device_index=prepared["index"])
 
     def train_step(self, batch: dict) -> dict:
         return self.step_prepared(self.prepare_batch(batch))

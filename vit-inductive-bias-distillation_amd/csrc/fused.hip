@@ -89,11 +89,11 @@ int basd_procrustes_finish_tuning(int fused) {
 
 // What basd_procrustes_forward_fused would launch for these arguments under the current hooks (host only, no HIP call;
 // pointers are only tested for presence and alignment): the fields of basd::plan::ProcrustesPlan in order.
-int basd_procrustes_plan_query(const BasdProcrustesArgs* a, long* out20) {
+static int plan_query(const BasdProcrustesArgs* a, long* out20, bool teacher_given) {
     using namespace basd::plan;
     BASD_CHECK_ARG(out20);
     ProcrustesPlan p;
-    BASD_TRY(procrustes_plan(a, g_transposed_cores, g_finish_fused, &p));
+    BASD_TRY(procrustes_plan(a, g_transposed_cores, g_finish_fused, &p, teacher_given));
     const long out[kPlanFields] = {p.center, p.project, p.slab_width, p.slabs, p.gram_split, p.chol, p.cores,
                                    p.svd, p.finish, p.rebuild_usigma, p.grad, p.usigma_in, p.tr_part_floats,
                                    p.w_borrow_floats, p.lds_center, p.lds_project, p.lds_gram, p.lds_chol,
@@ -101,6 +101,9 @@ int basd_procrustes_plan_query(const BasdProcrustesArgs* a, long* out20) {
     for (int i = 0; i < kPlanFields; ++i) out20[i] = out[i];
     return p.status();
 }
+int basd_procrustes_plan_query(const BasdProcrustesArgs* a, long* out20) { return plan_query(a, out20, false); }
+// The same for basd_procrustes_forward_cached: field 0 is 5 ("given"), fields 4, 13 and 14 are 0.
+int basd_procrustes_plan_query_cached(const BasdProcrustesArgs* a, long* out20) { return plan_query(a, out20, true); }
 
 // relational.py:22-50 for all extraction layers against the (mixed) teacher, forward and -- optionally -- the student
 // gradients for given upstream gradients; see BasdProcrustesArgs in include/basd_hip.h.  The routes are those of the
@@ -108,16 +111,20 @@ int basd_procrustes_plan_query(const BasdProcrustesArgs* a, long* out20) {
 // never answered with another route.  The stages with a single entry point (Grams, Cholesky, finalize) are simply
 // called: past their bounds they refuse for themselves, from the predicates the plan's status is made of, and the
 // call ends there as it does at a stage without a route.
-int basd_procrustes_forward_fused(const BasdProcrustesArgs* a, hipStream_t st) {
+// teacher_given (basd_procrustes_forward_cached): omega, omega_t and the teacher slot of g_all are inputs; the token
+// weights, the centring and the teacher Gram are not queued and tok_ptrs, attn_ptrs, mix, mu_t, tc, g_slabs not read.
+static int procrustes_call(const BasdProcrustesArgs* a, hipStream_t st, bool teacher_given) {
     using namespace basd::plan;
-    BASD_CHECK_ARG(a && a->student_ptrs && a->tok_ptrs && a->attn_ptrs && a->mix);
+    BASD_CHECK_ARG(a && a->student_ptrs);
+    if (teacher_given) BASD_CHECK_ARG(a->omega && a->omega_t && a->g_all);
+    else BASD_CHECK_ARG(a->tok_ptrs && a->attn_ptrs && a->mix);
     ProcrustesPlan p;
-    BASD_TRY(procrustes_plan(a, g_transposed_cores, g_finish_fused, &p));
+    BASD_TRY(procrustes_plan(a, g_transposed_cores, g_finish_fused, &p, teacher_given));
     const int E = (int)a->E, L = (int)a->L, G = (int)a->G, B = (int)a->B, n_s = (int)a->n_s;
     const int d_s = (int)a->d_s, d_t = (int)a->d_t, H = (int)a->H, A = (int)a->A, n_a = (int)a->n_a, n = (int)a->n;
     const int td = (int)a->t_dtype, sd = (int)a->s_dtype;
     // teacher side: token weights + mixed, centred teacher, once per group (G = 1: shared by all layers)
-    for (int g = 0; g < G; ++g) {
+    for (int g = 0; g < G && !teacher_given; ++g) {
         BASD_TRY(basd_token_weights(a->attn_ptrs, (int)a->a_dtype, a->mix + (long)g * L, L, a->a_sb, a->a_sh, a->a_sq,
                                     a->a_sk, B, H, A, (int)a->has_cls, n_a, n, n_s, a->atap0, a->atap1, a->alam,
                                     a->tap0, a->tap1, a->lam, a->omega + (long)g * B * n_s,
@@ -138,6 +145,8 @@ int basd_procrustes_forward_fused(const BasdProcrustesArgs* a, hipStream_t st) {
                 BASD_TRY(basd_teacher_center(a->tok_ptrs, td, a->mix + (long)g * L, L, a->t_sb, a->t_sn, a->t_sd, B, n, d_t,
                                              a->g0, a->g1, a->glam, a->omega_t + (long)g * B * n,
                                              a->mu_t + (long)g * B * d_t, a->tc + (long)g * B * n * d_t, st));
+            break;
+        case kCenterGiven:
             break;
         default:
             return BASD_EUNSUPPORTED;
@@ -162,7 +171,9 @@ int basd_procrustes_forward_fused(const BasdProcrustesArgs* a, hipStream_t st) {
     double* g_b = a->g_all + (long)EB * nn;
     double* l_b = a->l_all + (long)EB * nn;
     BASD_TRY(basd_gram_f64(a->a_prime, (long)n * d_s, n, d_s, EB, a->g_all, nn, st));
-    if (p.gram_split)
+    if (teacher_given) {
+        // g_b is the caller's (basd_teacher_cache_load): factored below with the student Grams, as in the uncached call
+    } else if (p.gram_split)
         BASD_TRY(basd_gram_f64_split(a->tc, (long)n * d_t, n, d_t, GB, (int)a->g_splits, a->g_slabs, g_b, st));
     else
         BASD_TRY(basd_gram_f64(a->tc, (long)n * d_t, n, d_t, GB, g_b, nn, st));
@@ -225,6 +236,8 @@ int basd_procrustes_forward_fused(const BasdProcrustesArgs* a, hipStream_t st) {
     }
     return BASD_OK;
 }
+int basd_procrustes_forward_fused(const BasdProcrustesArgs* a, hipStream_t st) { return procrustes_call(a, st, false); }
+int basd_procrustes_forward_cached(const BasdProcrustesArgs* a, hipStream_t st) { return procrustes_call(a, st, true); }
 
 // Events for ordering two streams from inside a library call (see basd_tridiag_ranked's mid_event).
 int basd_event_create(void** out) {

@@ -86,7 +86,8 @@ inline bool grad_fused_applies(int ptrs_aligned, int dtype, long sb, long sn, in
 }
 
 // ---- the plan ---------------------------------------------------------------------------------------------------
-enum Center { kCenterNone = 0, kCenterStreamV4, kCenterStream, kCenterMulti, kCenterPerGroup };
+// kCenterGiven: the teacher side is an input of the call (basd_procrustes_forward_cached), nothing is centred
+enum Center { kCenterNone = 0, kCenterStreamV4, kCenterStream, kCenterMulti, kCenterPerGroup, kCenterGiven };
 enum Project { kProjectNone = 0, kProjectMulti, kProjectPerLayer };
 enum Chol { kCholNone = 0, kCholLds, kCholBlocked };
 enum Cores { kCoresTransposed = 1, kCoresStacked };
@@ -111,19 +112,24 @@ struct ProcrustesPlan {
 constexpr int kPlanFields = 20;
 
 // Shapes and presence of the optional pointers are read from the call's own argument block; transposed_hook and
-// finish_hook are the settings of basd_procrustes_tuning / basd_procrustes_finish_tuning.
-inline int procrustes_plan(const BasdProcrustesArgs* a, int transposed_hook, int finish_hook, ProcrustesPlan* out) {
+// finish_hook are the settings of basd_procrustes_tuning / basd_procrustes_finish_tuning.  teacher_given: the plan of
+// basd_procrustes_forward_cached (G == 1 only) -- no centring, no teacher Gram; every later stage as without it.
+inline int procrustes_plan(const BasdProcrustesArgs* a, int transposed_hook, int finish_hook, ProcrustesPlan* out,
+                           bool teacher_given = false) {
     BASD_CHECK_ARG(a && out);
     const int E = (int)a->E, L = (int)a->L, G = (int)a->G, B = (int)a->B, n_s = (int)a->n_s, n_t = (int)a->n_t;
     const int d_s = (int)a->d_s, d_t = (int)a->d_t, n = (int)a->n;
     BASD_CHECK_ARG(E > 0 && L > 0 && (G == 1 || G == E) && B > 0 && n == (n_s < n_t ? n_s : n_t));
     BASD_CHECK_ARG(n > 0 && d_s > 0 && d_t > 0);
+    BASD_CHECK_ARG(!teacher_given || G == 1);
     const int EB = E * B;
     ProcrustesPlan p = {};
 
     // teacher side: all groups in one pass over the teacher layers where that applies
     const long borrow = stream_scratch_floats(G, B, n, d_t);
-    if (G > 1 && L >= 4 && borrow <= core_floats(E, B, n) && stream_applies(G, a->t_sd, B)) {
+    if (teacher_given) {
+        p.center = kCenterGiven;
+    } else if (G > 1 && L >= 4 && borrow <= core_floats(E, B, n) && stream_applies(G, a->t_sd, B)) {
         p.center = stream_v4_applies((int)a->t_dtype, a->g0 != nullptr, a->t_sb, a->t_sn, d_t, a->tc, a->W)
                        ? kCenterStreamV4 : kCenterStream;
         p.w_borrow_floats = borrow;
@@ -147,7 +153,7 @@ inline int procrustes_plan(const BasdProcrustesArgs* a, int transposed_hook, int
         p.lds_project = (long)(multi ? project_multi_lds(n_s) : project_lds(n_s));
     }
 
-    p.gram_split = a->g_slabs && a->g_splits > 1;
+    p.gram_split = !teacher_given && a->g_slabs && a->g_splits > 1;
     p.lds_gram = gram_fits(n) ? (long)gram_lds(n) : -1;
     p.chol = chol_in_lds(n) ? kCholLds : chol_blocked_fits(n) ? kCholBlocked : kCholNone;
     p.lds_chol = (long)(p.chol == kCholLds ? chol_lds(n) : chol_blocked_lds(n));
