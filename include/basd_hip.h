@@ -190,9 +190,25 @@ int basd_tridiag_ranked(float* a, long a_batch_stride, int n, int batch, float* 
  * BASD_TRIDIAG_{MEMBERS,PAD,LAG,THREADS,TAIL} environment variables, read ONCE when the library is loaded -- no
  * entry point calls getenv).  Negative = keep; reset != 0 restores the load-time values first.
  * members: workgroups per matrix in the shared stage; pad: workgroup-id padding between matrices; lag: member that
- * sleeps every step; threads: per member; tail: 0 = shared stage for the whole factorisation, 1 = the two-barrier
- * register-resident tail kernel (default), 2 = its four-barrier first form (kept for comparison tests). */
+ * sleeps every step; threads: per member; tail: 0 = shared stage for the whole factorisation, 1 (default) = orders
+ * 257..384 whole in the packed one-CU kernel, other orders shared stage + the register-resident tail kernel, 3 = shared
+ * stage + tail kernel for every order.  Any other tail: BASD_EINVAL from the call (nothing changes), ignored in the
+ * environment. */
 int basd_tridiag_tuning(int members, int pad, int lag, int threads, int tail, int reset);
+
+/* What basd_tridiag / _ranked / _ranked_gated would launch for that shape under the current tuning hooks (host only, no
+ * HIP call).  flags: 1 = the matrices can be read as 16-byte quads (16-byte aligned base, a_batch_stride % 4 == 0),
+ * 2 = ranks asked for, 4 = the gated entry point.  resident_budget: workgroups of the shared stage that may be resident
+ * together (the entry points take it from an occupancy query); <= 0 = the cap of 128.
+ * Returns what the entry point would: BASD_EINVAL (n < 2, batch < 1), BASD_EUNSUPPORTED (n > 4096; a gated call of a
+ * shape the gate does not take), else BASD_OK with
+ * out12: [0] front stage -- 0 none, 1 shared stage --, [1] back stage -- 0 none, 1 tail kernel, 2 packed kernel --,
+ * [2] j_stop (steps of the front stage), [3] shared-stage kernel -- 0 scalar, 1 quads, 2 quads with n % 8 == 0 --,
+ * [4] members per matrix, [5] workgroups of the shared stage, [6] its threads, [7] its dynamic LDS bytes ([3]..[7] are 0
+ * without a front stage), [8] ranks -- 0 none, 1 by the back stage's workgroups, 2 by a separate launch --, [9] the
+ * gated entry point takes the shape, [10] offset of the 8 status words in the workspace, [11]
+ * basd_tridiag_workspace_bytes(n, batch). */
+int basd_tridiag_plan_query(int n, int batch, int flags, int resident_budget, int* out12);
 
 /* All eigenvalues (descending) of the tridiagonals by Sturm-sequence bisection. */
 int basd_tridiag_eigenvalues(const float* d, const float* e, int n, int batch, float* vals_desc, hipStream_t stream);

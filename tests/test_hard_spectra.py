@@ -208,11 +208,10 @@ def oracle_rank(ev, M, n, cap):
 
 
 # 45, 200: tridiag_tail2_kernel runs the whole factorisation; 320, 384: tridiag_packed_kernel; 448: the shared stage
-# (whose polling and lock-step depend on step, member and tag only, never on the matrix values) followed by tail2;
-# 200 with tail=2: the four-barrier tail kernel.  `blocks` and `diag` give each of the four copies of the reflector
-# code steps with xn2 == 0.
+# (whose polling and lock-step depend on step, member and tag only, never on the matrix values) followed by tail2.
+# `blocks` and `diag` give each copy of the reflector code steps with xn2 == 0.
 @gpu
-@pytest.mark.parametrize("n,tail", [(45, None), (200, None), (320, None), (384, None), (448, None), (200, 2)])
+@pytest.mark.parametrize("n,tail", [(45, None), (200, None), (320, None), (384, None), (448, None)])
 def test_tridiag_route_on_hard_spectra(n, tail, tuning):
     """One batch per order: eigenvalues, leading eigenvectors (requested per family), the factorisation itself and the
     Marchenko-Pastur ranks.  Before the pivot rule of tridiag_invit_kernel followed slagts this failed on `zero` at every

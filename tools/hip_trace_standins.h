@@ -1,7 +1,8 @@
 // Stand-ins for the slice of the HIP runtime that a compiled .hip object of csrc/ uses, so that such objects link into
 // a plain program and their host side runs without a GPU (tools/jacobi_dispatch_trace.cpp,
-// tools/procrustes_dispatch_trace.cpp).  The stand-ins launch nothing: they record the kernel name, grid, block and
-// dynamic LDS bytes of every launch, every function attribute that is set and the byte count of every fill / copy.
+// tools/procrustes_dispatch_trace.cpp, tools/tridiag_dispatch_trace.cpp).  The stand-ins launch nothing: they record the
+// kernel name, grid, block and dynamic LDS bytes of every launch, every function attribute that is set, the byte count
+// of every fill / copy and every event that is recorded.
 // Runs of identical consecutive records (the rounds of a block solver) are folded into one line with a count.
 // Include once, in the one translation unit of the tracer.
 #pragma once
@@ -95,6 +96,11 @@ int hipMemcpyAsync(void*, const void*, size_t bytes, int kind, hipStream_t) {
     record("memcpy kind=" + std::to_string(kind) + " bytes=" + std::to_string(bytes));
     return 0;
 }
+// the device that occupancy-sized launches see: 256 CUs, one workgroup of any kernel per CU
+int hipGetDevice(int* device) { *device = 0; return 0; }
+int hipDeviceGetAttribute(int* value, int, int) { *value = 256; return 0; }
+int hipOccupancyMaxActiveBlocksPerMultiprocessor(int* blocks, const void*, int, size_t) { *blocks = 1; return 0; }
+int hipEventRecord(void*, hipStream_t) { record("event record"); return 0; }
 int hipEventCreateWithFlags(void**, unsigned) { return 0; }
 int hipEventDestroy(void*) { return 0; }
 int hipStreamWaitEvent(hipStream_t, void*, unsigned) { return 0; }

@@ -2,6 +2,7 @@
 // boundaries of every step (compile with -DBASD_TAIL_DBG), and a bit-level fingerprint of the factorisation that must
 // not depend on -DBASD_TAIL_JITTER (waves asleep at the phase boundaries; a -DBASD_TAIL_DBG build is for TIMING only:
 // its scalar-memory stamps disturb the hand-counted LDS waits and the factorisation it computes is garbage).  One matrix.
+// usage: tail_phase_probe [n = 256] [tail = 1 | 3 | 0, as basd_tridiag_tuning]
 #include "../../vit-inductive-bias-distillation_amd/csrc/tridiag.hip"
 #include <stdio.h>
 #include <vector>

@@ -39,6 +39,7 @@ SIGNATURES = {
     "basd_sort_extract": [vp, i64, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp],
     "basd_tridiag_workspace_bytes": [i32, i32],
     "basd_tridiag_tuning": [i32, i32, i32, i32, i32, i32],
+    "basd_tridiag_plan_query": [i32, i32, i32, i32, vp],
     "basd_tridiag": [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp],
     "basd_tridiag_ranked": [vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, f64, i32, vp, vp, vp, vp],
     "basd_tridiag_ranked_gated": [vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, f64, i32, vp, vp, vp, C.c_uint, i32, vp],

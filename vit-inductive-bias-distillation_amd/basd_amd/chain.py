@@ -142,8 +142,10 @@ class SelectorChainPlan:
     def __init__(self, students, teachers, mode: int, streams, fact_stream=None):
         s, t = students[0], teachers[0]
         self.fact_stream = fact_stream
-        # the early launch needs the one-kernel factorisation (orders 257..384) and mode 3
-        self.early = bool(EARLY_LAUNCH and fact_stream is not None and mode == 3 and 256 < s.shape[2] <= 384)
+        # the early launch needs mode 3 and an order that the gated factorisation (2 L matrices, ranked) takes
+        plan = (C.c_int * 12)()
+        gated = _lib.query("basd_tridiag_plan_query", s.shape[2], 2 * len(teachers), 2 | 4, 0, C.cast(plan, C.c_void_p)) == 0
+        self.early = bool(EARLY_LAUNCH and fact_stream is not None and mode == 3 and gated)
         self.E, self.L = len(students), len(teachers)
         self.B, self.n_s, self.d_s = s.shape
         _, self.n_t, self.d_t = t.shape

@@ -11,6 +11,7 @@
 // step's largest rank) and every kernel takes the actual rank from device memory -- correct for any hint >= the
 // largest rank; the caller re-queues the tail (basd_selector_chain_tail) in the rare step where the rank grew past it.
 #include "basd_common.h"
+#include "tridiag_plan.h"
 #include "../../include/basd_hip.h"
 #include <stdlib.h>
 
@@ -367,8 +368,8 @@ int basd_selector_chain(const BasdSelectorChain* a) {
         BASD_TRY(basd_tridiag(a->grams + 2L * L * nn, nn, n, E, a->d + 2L * L * n, a->e + 2L * L * n,
                               a->tau + 2L * L * n, a->vh + 2L * L * nn, a->tri_work_s, ss));
         if (a->student_status_mirror) {
-            // status words of the student factorisation (last 32 bytes of its workspace): read by the host a step later
-            const char* err = (const char*)a->tri_work_s + basd_tridiag_workspace_bytes(n, E) - 32;
+            // status words of the student factorisation: read by the host a step later
+            const char* err = (const char*)a->tri_work_s + basd::plan::tridiag_workspace(n, E).status_off;
             BASD_HIP(hipMemcpyAsync(a->student_status_mirror, err, 32, hipMemcpyDeviceToHost, ss));
         }
         BASD_HIP(hipEventRecord((hipEvent_t)a->ev_student, ss));

@@ -13,6 +13,7 @@
 // One workgroup per matrix; the matrix stays in L2 and is streamed row-wise (coalesced), the Householder
 // vector lives in LDS.  Everything is fp32, like LAPACK's ssytd2 / sstebz / sstein it restates.
 #include "basd_common.h"
+#include "tridiag_plan.h"
 #include <stdlib.h>
 #include <atomic>
 
@@ -92,7 +93,6 @@ __device__ __forceinline__ void load8_rows(float4 (&a)[8], const float* p0, cons
 __device__ long long g_tail_dbg[2 * 8 * 2 * 1024];
 #endif
 constexpr int TRI_RB = 8;      // rows per group: RB independent load streams keep L2 latency covered
-constexpr int TRI_BLK = 32;    // rows per ownership block (4 groups)
 
 // grid = P * batch_pad workgroups of 1024 threads; workgroup id = p * batch_pad + z works on matrix z as
 // member p of P (ids that differ by a multiple of 8 are dealt to one XCD: the P members share an L2).
@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(1024) tridiag_kernel(float* __restrict__ A, lo
         form_reflector(0, block_sum_lds(part, red, nw));
     }
     // j_stop < n - 1: only steps [0, j_stop) are done here; the trailing block of order n - j_stop goes on in
-    // tridiag_tail_kernel (registers of one CU, no exchange), which gets the matrix rows as stored by the last pass
+    // tridiag_tail2_kernel (registers of one CU, no exchange), which gets the matrix rows as stored by the last pass
     // plus the still pending rank-2 update (v, w) of step j_stop - 1 through `pend`.
     for (int j = 0; j < n - 1 && j < j_stop; ++j) {
         const int r0 = j + 1;
@@ -352,21 +352,29 @@ __global__ void __launch_bounds__(1024) tridiag_kernel(float* __restrict__ A, lo
 }
 
 // ---------------------------------------------------------------------------
-// The same factorisation for a trailing block that fits ONE CU's registers: steps [j0, n-1) on the block of order
-// m = n - j0 <= 64 * CPL, one workgroup of 64 * WAVES threads per matrix, no exchange with anybody.
-// Thread (wave w, lane l) keeps M[w + WAVES * i][l + 64 * k] (i < RPW, k < CPL) in registers for the whole
-// factorisation; a step is one pass over the registers (pending rank-2 update of the previous step applied lazily,
-// product with the current reflector accumulated on the way) and four workgroup barriers:
-//   pass      a' = a - v_r w_c - w_r v_c ;  acc_c += a' u_r           (u_r, v_r, w_r wave-uniform: LDS broadcasts)
-//   A         per-wave column partials -> LDS;  threads c < m: p_c = tau * sum over waves
-//   B         gamma = -tau/2 p.u ;  w = p + gamma u ;  next pivot row (captured by the pass) updated analytically
-//   C         its norm -> reflector of the next step (d, e, tau written)
-//   D         u, v, w published;  reflector row stored to Vh
+// The tail stage: the same factorisation for a trailing block that fits ONE CU's registers -- steps [j0, n-1) on the
+// block of order m = n - j0 <= 256, one workgroup per matrix, no exchange with anybody.  The block stays in registers
+// for the whole factorisation; a step is one pass over them (pending rank-2 update of the previous step applied lazily,
+// product with the current reflector accumulated on the way) and a short scalar part (step j, local numbering, r0 = j + 1):
+//   pass       a' = a - (v_r w_c + w_r v_c) ;  acc_c += a' u_r         (one fma each; u_r, v_r, w_r wave-uniform)
+//   partials   per-wave column partials -> LDS;  p_c = tau * (sum over the waves, in wave order)
+//   w          gamma = -tau/2 p.u ;  w = gamma u + p ;  the next pivot row (captured by the pass) updated analytically:
+//              col_c = cap_c - (u_c w_{r0} + w_c)
+//   reflector  of step j + 1, from col (row r0 of the updated block): alpha = col_{r0+1}, xn2 = sum_{c > r0+1} col_c^2;
+//              xn2 == 0: nothing to reduce (beta = alpha, tau = 0, u = e_{r0+1}), else
+//              beta = -sign(alpha) sqrt(alpha^2 + xn2), tau = (beta - alpha) / beta, u_{r0+1} = 1,
+//              u_c = col_c / (alpha - beta) -- with the 1-ulp hardware sqrt and reciprocal (IEEE sqrtf and division are
+//              ~30-instruction software sequences, three of them in a row on the dependent chain of every step);
+//              d_{r0} = col_{r0}, e_{r0} = beta, tau_{r0} = tau written
+//   publish    v = u and w of this step, u of the next;  its reflector row stored to Vh (zeros, then u)
 // It is the algorithm of tridiag_kernel run on the transpose (rows take the part of columns: the matrix is
 // symmetric), with the row-wise sums replaced by per-lane column sums so that no cross-lane reduction sits in the
-// pass.  Rows that are already reduced are skipped (wave-uniform), so the pass shrinks with the trailing block.
-// n <= 64 * CPL: the whole factorisation (j0 = 0, pend = nullptr) -- nothing spins anywhere.
-// n >  64 * CPL: tridiag_kernel does steps [0, j0) and hands over the pending update (pend: v, w of step j0 - 1).
+// pass.  Rows that are already reduced are skipped, so the pass shrinks with the trailing block.
+// n <= 256: the whole factorisation (j0 = 0, pend = nullptr) -- nothing spins anywhere.
+// n >  256: tridiag_kernel does steps [0, j0) and hands over the pending update (pend: v, w of step j0 - 1).
+// At the end the workgroup computes the Marchenko-Pastur rank of the first `count` matrices of the batch right here: the
+// host is waiting for it, and this workgroup already owns a CU -- a separate launch would queue for wave slots behind the
+// throughput kernels of the other streams (rocprofv3, cfg-2: 0.17-0.49 ms inside a step for 0.05 ms of work).
 // ---------------------------------------------------------------------------
 // Marchenko-Pastur rank of the tridiagonal (dz, ez) by the whole workgroup (defined below, next to the Sturm count).
 struct MpRankOut {
@@ -379,192 +387,13 @@ struct MpRankOut {
 __device__ __forceinline__ void mp_rank_block(const float* dz, const float* ez, int n, int z, const MpRankOut& o,
                                               float* thr_out);
 
-template <int WAVES, int RPW, int CPL>
-__global__ void __launch_bounds__(64 * WAVES) tridiag_tail_kernel(float* __restrict__ A, long a_batch_stride, int n,
-                                                                  int j0, const float* __restrict__ pend,
-                                                                  float* __restrict__ d, float* __restrict__ e,
-                                                                  float* __restrict__ tau_out,
-                                                                  float* __restrict__ Vh, MpRankOut rk) {
-    constexpr int MMAX = 64 * CPL;
-    static_assert(WAVES * RPW >= MMAX, "every row needs an owner");
-    static_assert(WAVES * 64 >= MMAX, "one thread per column in the vector phases");
-    __builtin_amdgcn_s_setprio(3);
-    __shared__ float u[MMAX], v[MMAX], w[MMAX], cap[MMAX], pw[MMAX], col[MMAX];
-    __shared__ float dloc[MMAX], eloc[MMAX];      // d, e of the local steps (for the rank at the end)
-    __shared__ float part[WAVES][MMAX];
-    __shared__ float red[2][16];
-    const int z = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m = n - j0;
-    float* Az = A + (long)z * a_batch_stride;
-    float* dz = d + (long)z * n;
-    float* ez = e + (long)z * n;
-    float* tz = tau_out + (long)z * n;
-    float* Vz = Vh + (long)z * n * n;
-    const float* pz = pend ? pend + (long)z * 2 * n : nullptr;
-
-    // ---- load the trailing block (pending update applied), zero padded to MMAX
-    float a[RPW][CPL];
-#pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        const int r = wave + WAVES * i;
-        const float vr = (pz && r < m) ? pz[j0 + r] : 0.f, wr = (pz && r < m) ? pz[n + j0 + r] : 0.f;
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) {
-            const int c = lane + 64 * k;
-            float x = 0.f;
-            if (r < m && c < m) {
-                x = Az[(long)(j0 + r) * n + j0 + c];
-                if (pz) x -= fmaf(vr, pz[n + j0 + c], wr * pz[j0 + c]);
-            }
-            a[i][k] = x;
-        }
-    }
-    for (int c = tid; c < MMAX; c += 64 * WAVES) {
-        u[c] = 0.f;
-        v[c] = 0.f;
-        w[c] = 0.f;
-        cap[c] = 0.f;
-    }
-    // row 0 of the block: what the first reflector is built from
-    if (wave == 0) {
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) col[lane + 64 * k] = a[0][k];
-    }
-    __syncthreads();
-
-    // reflector of local step jl from col[] (row jl of the current block, entries >= jl), as tridiag_kernel's
-    // form_reflector; threads c < MMAX write u; d / e / tau by one thread.  xn2 = sum_{c > jl + 1} col[c]^2.
-    float tau = 0.f;
-    auto form_reflector = [&](int jl, float xn2) {
-        const int r0 = jl + 1;
-        const float alpha = col[r0];
-        float beta = alpha;
-        tau = 0.f;
-        if (xn2 > 0.f) {
-            // 1-ulp hardware sqrt / reciprocal: IEEE sqrtf and division are ~30-instruction software sequences, three
-            // of them in a row on the dependent chain of every step
-            beta = -copysignf(__builtin_amdgcn_sqrtf(fmaf(alpha, alpha, xn2)), alpha);
-            tau = (beta - alpha) * __builtin_amdgcn_rcpf(beta);
-        }
-        if (tid == 0) {
-            dz[j0 + jl] = dloc[jl] = col[jl];
-            ez[j0 + jl] = eloc[jl] = beta;
-            tz[j0 + jl] = tau;
-        }
-        const float scal = tau != 0.f ? __builtin_amdgcn_rcpf(alpha - beta) : 0.f;
-        if (tid < MMAX) u[tid] = tid < r0 ? 0.f : (tid == r0 ? 1.f : col[tid] * scal);
-    };
-    auto block_sum4 = [&](float x, float* slot) {      // sum over the threads < MMAX (whole waves), one barrier
-        x = wave_sum(x);
-        if (lane == 0 && tid < MMAX) slot[wave] = x;
-        __syncthreads();
-        float r = 0.f;
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) r += slot[i];
-        return r;
-    };
-    {
-        const float cv = tid < MMAX ? col[tid] : 0.f;
-        const float xn2 = block_sum4((tid > 1 && tid < MMAX) ? cv * cv : 0.f, red[0]);
-        form_reflector(0, xn2);
-        __syncthreads();
-    }
-    // the reflector row of step j in Vh: zeros up to column j, then u
-    auto store_reflector = [&](int jl) {
-        float* vrow = Vz + (long)(j0 + jl) * n;
-        for (int c = tid; c < n; c += 64 * WAVES) vrow[c] = c < j0 ? 0.f : u[c - j0];
-    };
-    store_reflector(0);
-
-    for (int jl = 0; jl < m - 1; ++jl) {
-        const int r0 = jl + 1;
-        // ---- pass over the registers
-        float vc[CPL], wc[CPL], acc[CPL];
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) {
-            vc[k] = v[lane + 64 * k];
-            wc[k] = w[lane + 64 * k];
-            acc[k] = 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < RPW; ++i) {
-            const int r = wave + WAVES * i;
-            if (r >= r0 && r < m) {                      // wave-uniform
-                const float ur = u[r], vr = v[r], wr = w[r];
-#pragma unroll
-                for (int k = 0; k < CPL; ++k) {
-                    a[i][k] -= fmaf(vr, wc[k], wr * vc[k]);
-                    acc[k] = fmaf(a[i][k], ur, acc[k]);
-                }
-                if (r == r0) {                           // the row the next reflector is built from
-#pragma unroll
-                    for (int k = 0; k < CPL; ++k) cap[lane + 64 * k] = a[i][k];
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) part[wave][lane + 64 * k] = acc[k];
-        __syncthreads();                                                                   // A
-        float pc = 0.f, uc = 0.f;
-        if (tid < MMAX) {
-            float sacc = 0.f;
-#pragma unroll
-            for (int q = 0; q < WAVES; ++q) sacc += part[q][tid];
-            pc = tau * sacc;
-            uc = u[tid];
-            pw[tid] = pc;
-        }
-        const float gamma = -0.5f * tau * block_sum4(tid < MMAX ? pc * uc : 0.f, red[1]);   // B (publishes pw)
-        float wn = 0.f, part2 = 0.f;
-        if (tid < MMAX) {
-            const float w0 = pw[r0] + gamma;             // u[r0] = 1
-            if (tid >= r0) {
-                wn = fmaf(gamma, uc, pc);
-                const float cn = cap[tid] - fmaf(uc, w0, wn);
-                col[tid] = cn;
-                if (tid > r0 + 1) part2 = cn * cn;
-            }
-        }
-        const float xn2 = block_sum4(part2, red[0]);                                        // C (publishes col)
-        if (tid < MMAX) {
-            v[tid] = uc;
-            w[tid] = wn;
-        }
-        if (jl + 1 < m - 1) form_reflector(jl + 1, xn2);
-        __syncthreads();                                                                    // D
-        if (jl + 1 < m - 1) store_reflector(jl + 1);
-    }
-    if (tid == 0) {
-        dz[n - 1] = dloc[m - 1] = col[m - 1];
-        ez[n - 1] = eloc[m - 1] = 0.f;
-        tz[n - 1] = 0.f;
-    }
-    for (int c = tid; c < n; c += 64 * WAVES) Vz[(long)(n - 1) * n + c] = 0.f;
-    // The Marchenko-Pastur rank of the first `count` matrices of the batch right here: the host is waiting for it, and
-    // this workgroup already owns a CU -- a separate launch would queue for wave slots behind the throughput kernels
-    // of the other streams (rocprofv3, cfg-2: 0.17-0.49 ms inside a step for 0.05 ms of work).  The tridiagonal is
-    // staged in LDS (the partials buffer is free now); entries of the first stage come from global memory.
-    if (rk.rank_out && z < rk.count && 2 * n <= 8 * MMAX) {
-        __syncthreads();
-        float* dl = &part[0][0];
-        float* el = dl + n;
-        for (int c = tid; c < n; c += 64 * WAVES) {
-            dl[c] = c < j0 ? dz[c] : dloc[c - j0];
-            el[c] = c < j0 ? ez[c] : eloc[c - j0];
-        }
-        __syncthreads();
-        mp_rank_block(dl, el, n, z, rk, nullptr);
-    }
-}
-
 // ---------------------------------------------------------------------------
-// tridiag_tail_kernel, second form (8 waves).  What limits a step of the first form is not the barriers (~100 cycles
-// each) but INSTRUCTION ISSUE and the LDS return path: a SIMD issues one wave64 VALU instruction per 4 cycles, the waves
-// of a SIMD share it, and s_memtime stamps (tools/probe/tail_phase_probe.hip) put the pass at 1500-2300 cycles and the
-// scalar part of the step -- which the threads < m of four waves ran between four barriers -- at ~3000.  Per matrix row
-// the first form issues 8 packed FMAs, 10 v_mov that splat (u_r, v_r, w_r) into register pairs, and a uniform branch.
-// Here
+// tridiag_tail2_kernel: the tail stage on 8 waves.  Written the plain way (16 waves, one matrix row at a time, the
+// scalar part on the threads < m of four waves between four workgroup barriers -- the form this kernel replaced) a step
+// is limited not by the barriers (~100 cycles each) but by INSTRUCTION ISSUE and the LDS return path: a SIMD issues one
+// wave64 VALU instruction per 4 cycles, the waves of a SIMD share it, and s_memtime stamps
+// (tools/probe/tail_phase_probe.hip) put the pass at 1500-2300 cycles and the scalar part at ~3000; per matrix row that
+// form issues 8 packed FMAs, 10 v_mov that splat (u_r, v_r, w_r) into register pairs, and a uniform branch.  Here
 //   * rows are consumed in pairs (r_a = wave + 16 P, r_b = r_a + 8); per wave and pair LDS holds (v_a, w_a, v_b, w_b)
 //     and (u_a, u_b), fetched one pair ahead with one b128 + one b64 read, and a wave-uniform operand of a packed FMA is
 //     taken from either half of a register pair with op_sel / op_sel_hi: a pair of rows is 12 v_pk_fma_f32 and nothing
@@ -581,7 +410,7 @@ __global__ void __launch_bounds__(64 * WAVES) tridiag_tail_kernel(float* __restr
 //     the issue slots of every wave; d, e, tau collect in LDS and are stored once at the end; the reflector row is
 //     stored by the LAST wave behind barrier B;
 //   * two workgroup barriers per step: A publishes the partials and the captured row, B the operands of the next pass.
-// Same arithmetic as the first form (same update order, same reflector formulas).
+// The arithmetic is that of the description above: same update order, same reflector formulas.
 // ---------------------------------------------------------------------------
 #ifdef BASD_TAIL_DBG
 // s_memtime stamps at the phase boundaries (tools/probe/tail_phase_probe.hip)
@@ -593,7 +422,7 @@ __global__ void __launch_bounds__(64 * WAVES) tridiag_tail_kernel(float* __restr
 #define TAIL_CLOCKS(which) do { } while (0)
 #endif
 // test builds (EXTRA=-DBASD_TAIL_JITTER): waves fall asleep at the phase boundaries in a wave- and step-dependent pattern;
-// results must not change by a bit (tools/probe/tail_phase_probe.hip checks against the four-barrier kernel)
+// results must not change by a bit (tools/probe/tail_phase_probe.hip prints a fingerprint to compare between builds)
 #ifdef BASD_TAIL_JITTER
 #define TAIL_JITTER(slot) do { if (((wave * 7 + jl * 3 + (slot)) % 5) == 0) __builtin_amdgcn_s_sleep(60); } while (0)
 #else
@@ -955,7 +784,7 @@ __global__ void __launch_bounds__(512) tridiag_tail2_kernel(float* __restrict__ 
 // The pass starts at the first batch of 4 row pairs that still has a live row (rows < r0 are finished: their u_r is
 // 0, so whatever the pass does to them is never read).
 // ---------------------------------------------------------------------------
-constexpr int PK_WAVES = 8, PK_NMAX = 384, PK_RPW = PK_NMAX / PK_WAVES, PK_PAIRS = PK_RPW / 2, PK_CH = PK_NMAX / 64;
+constexpr int PK_RPW = PK_NMAX / PK_WAVES, PK_PAIRS = PK_RPW / 2, PK_CH = PK_NMAX / 64;
 __host__ __device__ constexpr int pk_boff(int kb) { return 4 * (kb * PK_CH - kb * (kb - 1) / 2); }   // 0, 24, 44, 60, 72, 80
 __host__ __device__ constexpr int pk_idx(int P, int k) { return pk_boff(P >> 2) + (P & 3) * (PK_CH - (P >> 2)) + (k - (P >> 2)); }
 static_assert(pk_boff(6) == 84, "84 packed registers");
@@ -2081,36 +1910,31 @@ extern "C" {
 // Householder tridiagonalisation of `batch` symmetric matrices (destroyed).  d, e, tau: (batch, n);
 // vh: (batch, n, n) reflector rows.
 //
-// Two stages.  The trailing block of order <= 256 is factored by tridiag_tail_kernel in the registers of ONE CU per
+// Two stages.  The trailing block of order <= 256 is factored by tridiag_tail2_kernel in the registers of ONE CU per
 // matrix (no exchange, nothing spins: n <= 256 never leaves that kernel).  For n > 256 the first n - 256 steps --
 // where one CU's issue rate and L2 bandwidth bound a step -- run on tridiag_kernel with the matrix shared by up to 16
 // workgroups ("members", one 32-row block each at n = 384; measured at n = 384, 6 matrices, whole factorisation:
 // 3.12 ms with 1 member, 1.95 with 4, 1.63 with 12).  Members poll each other's granules, so all of them must be
-// resident: at most 128 workgroups per launch (two concurrent launches still fit the 256 CUs).
-static int nblk_of(int n) { return (n + TRI_BLK - 1) / TRI_BLK; }
-
-constexpr int TRI_TAIL_MAX = 256;      // order of the register-resident trailing block (64 * CPL of the tail kernel)
+// resident: at most 128 workgroups per launch (two concurrent launches still fit the 256 CUs).  Which stages a call
+// takes and how they are launched: plan::tridiag_plan (tridiag_plan.h).
 
 // Tuning / test hooks, read ONCE when the library is loaded (never inside an entry point):
 //   BASD_TRIDIAG_MEMBERS  members per matrix in the shared stage (default: one per 32-row block, <= 16)
 //   BASD_TRIDIAG_PAD      workgroup-id padding between matrices (scatters the members over XCDs; tests)
 //   BASD_TRIDIAG_LAG      member that sleeps every step (tests the hand-off under uneven progress)
 //   BASD_TRIDIAG_THREADS  threads per member
-//   BASD_TRIDIAG_TAIL     1 (default): orders 257..384 whole in tridiag_packed_kernel (one CU's registers, upper triangle),
-//                         other orders shared stage + tridiag_tail2_kernel; 3: shared stage + tail2 for every order (the
-//                         round-2 path); 2: the same with the four-barrier tail kernel; 0: whole factorisation in the
-//                         shared stage (the round-1 path).  Tests compare all of them.
-struct TridiagTuning {
-    int members = 0, pad = -1, lag = -1, threads = 0, tail = 1;
-    TridiagTuning() {
-        if (const char* s = getenv("BASD_TRIDIAG_MEMBERS")) members = atoi(s);
-        if (const char* s = getenv("BASD_TRIDIAG_PAD")) pad = atoi(s);
-        if (const char* s = getenv("BASD_TRIDIAG_LAG")) lag = atoi(s);
-        if (const char* s = getenv("BASD_TRIDIAG_THREADS")) threads = atoi(s);
-        if (const char* s = getenv("BASD_TRIDIAG_TAIL")) tail = atoi(s);
-    }
-};
-static TridiagTuning g_tuning;
+//   BASD_TRIDIAG_TAIL     0, 1 (default) or 3: see plan::TridiagTuning; any other value is ignored
+static plan::TridiagTuning tuning_from_env() {
+    plan::TridiagTuning t;
+    if (const char* s = getenv("BASD_TRIDIAG_MEMBERS")) t.members = atoi(s);
+    if (const char* s = getenv("BASD_TRIDIAG_PAD")) t.pad = atoi(s);
+    if (const char* s = getenv("BASD_TRIDIAG_LAG")) t.lag = atoi(s);
+    if (const char* s = getenv("BASD_TRIDIAG_THREADS")) t.threads = atoi(s);
+    if (const char* s = getenv("BASD_TRIDIAG_TAIL"))
+        if (plan::tail_is_valid(atoi(s))) t.tail = atoi(s);
+    return t;
+}
+static plan::TridiagTuning g_tuning = tuning_from_env();
 static const int g_pk_clocks = getenv("BASD_TRIDIAG_CLOCKS") ? atoi(getenv("BASD_TRIDIAG_CLOCKS")) : 0;   // diagnostics
 
 // Workgroups of one shared-stage launch that may spin on each other: all of them must be resident together, beside
@@ -2121,14 +1945,14 @@ static const int g_pk_clocks = getenv("BASD_TRIDIAG_CLOCKS") ? atoi(getenv("BASD
 static int tridiag_resident_budget(int n) {
     static std::atomic<int> cached_n{0}, cached_budget{0};
     if (cached_n.load(std::memory_order_acquire) == n) return cached_budget.load(std::memory_order_relaxed);
-    int dev = 0, cus = 0, per_cu = 0, budget = 128;
+    int dev = 0, cus = 0, per_cu = 0, budget = plan::TRI_BUDGET_CAP;
     if (hipGetDevice(&dev) == hipSuccess &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)tridiag_kernel<true, true>, 1024,
                                                      sizeof(float) * 9 * (size_t)n) == hipSuccess &&
         cus > 0 && per_cu > 0) {
         budget = per_cu * cus / 2;
-        if (budget > 128) budget = 128;
+        if (budget > plan::TRI_BUDGET_CAP) budget = plan::TRI_BUDGET_CAP;
     }
     if (const char* sb = getenv("BASD_TRIDIAG_BUDGET")) budget = atoi(sb);      // experiment hook, read once per n
     cached_budget.store(budget, std::memory_order_relaxed);
@@ -2136,21 +1960,13 @@ static int tridiag_resident_budget(int n) {
     return budget;
 }
 
-static int tridiag_members(int n, int batch) {
-    const int nblk = nblk_of(n);
-    int p = g_tuning.members > 0 ? g_tuning.members : nblk;
-    if (p > 16) p = 16;
-    const int budget = tridiag_resident_budget(n);
-    while (p > 1 && p * batch > budget) --p;
-    if (p > nblk) p = nblk;
-    return p < 1 ? 1 : p;
-}
-
 // Test / tuning hook: overrides the values read from the environment at load time (negative = keep the current value;
-// `reset` != 0 first restores the load-time environment values).  Process-wide; meant for tests and experiments, not for
-// use while factorisations are being queued from other threads.
+// `reset` != 0 first restores the load-time environment values).  A `tail` that names no route is BASD_EINVAL and
+// nothing changes.  Process-wide; meant for tests and experiments, not for use while factorisations are being queued
+// from other threads.
 int basd_tridiag_tuning(int members, int pad, int lag, int threads, int tail, int reset) {
-    if (reset) g_tuning = TridiagTuning();
+    BASD_CHECK_ARG(tail < 0 || plan::tail_is_valid(tail));
+    if (reset) g_tuning = tuning_from_env();
     if (members >= 0) g_tuning.members = members;
     if (pad >= 0) g_tuning.pad = pad;
     if (lag >= 0) g_tuning.lag = lag;
@@ -2159,38 +1975,43 @@ int basd_tridiag_tuning(int members, int pad, int lag, int threads, int tail, in
     return BASD_OK;
 }
 
-long basd_tridiag_workspace_bytes(int n, int batch) {
-    // per matrix: 2 parities x n granules of 16 bytes, then the pending (v, w) handed to the tail stage; at the very
-    // end the status word and 7 words of give-up trace
-    return (long)batch * 2 * n * 16 + (long)batch * 2 * n * 4 + 32;
+long basd_tridiag_workspace_bytes(int n, int batch) { return plan::tridiag_workspace(n, batch).bytes; }
+
+// What a factorisation of that shape would launch under the current tuning hooks; no HIP call.  flags: 1 = the matrices
+// can be read as 16-byte quads, 2 = ranks asked for, 4 = the gated entry point.  resident_budget <= 0: the cap of 128.
+// Returns what the entry point would (BASD_EUNSUPPORTED also for a gated call of a shape the gate does not take); out12
+// is written where that is BASD_OK, in the order documented in basd_hip.h.
+int basd_tridiag_plan_query(int n, int batch, int flags, int resident_budget, int* out12) {
+    BASD_CHECK_ARG(out12 && (flags & ~7) == 0);
+    const plan::TridiagPlan p = plan::tridiag_plan(n, batch, flags & 1, flags & 2, flags & 4, g_tuning,
+                                                   resident_budget > 0 ? resident_budget : plan::TRI_BUDGET_CAP);
+    if (p.status != BASD_OK) return p.status;
+    BASD_CHECK_ARG(p.ws.bytes <= 0x7fffffffL);           // the two byte counts are reported as int
+    const int out[12] = {p.front, p.back, p.j_stop, p.variant, p.members, p.grid, p.threads, (int)p.lds, p.ranks,
+                         (int)p.gated_ok, (int)p.ws.status_off, (int)p.ws.bytes};
+    for (int i = 0; i < 12; ++i) out12[i] = out[i];
+    return BASD_OK;
 }
 
 static int tridiag_impl(float* a, long a_batch_stride, int n, int batch, float* d, float* e, float* tau, float* vh,
                         void* work, MpRankOut rk, hipStream_t stream, hipEvent_t mid_event = nullptr,
                         const unsigned* go_flag = nullptr, unsigned go_value = 0, int go_budget = 0) {
-    BASD_CHECK_ARG(a && d && e && tau && vh && work && n > 1 && batch > 0);
+    BASD_CHECK_ARG(a && d && e && tau && vh && work);
     BASD_CHECK_ARG((((uintptr_t)work) & 15) == 0);
-    if (n > 4096) return BASD_EUNSUPPORTED;
-    const long gran_bytes = (long)batch * 2 * n * 16;
+    const bool quads = (a_batch_stride & 3) == 0 && (((uintptr_t)a) & 15) == 0;
+    // the occupancy query only for a call whose plan has a shared stage (a gated call never has one)
+    const int budget = !go_flag && plan::tridiag_needs_budget(n, batch, g_tuning.tail) ? tridiag_resident_budget(n) : 0;
+    const plan::TridiagPlan p = plan::tridiag_plan(n, batch, quads, rk.rank_out != nullptr, go_flag != nullptr, g_tuning, budget);
+    if (p.status != BASD_OK) return p.status;
     uint4* xg = (uint4*)work;
-    float* pend = (float*)((char*)work + gran_bytes);
-    int* err = (int*)((char*)work + gran_bytes + (long)batch * 2 * n * 4);
-    const bool tail = g_tuning.tail != 0;
-    // orders 257..384: the whole factorisation in one CU's registers (upper triangle): no shared stage at all
-    const bool packed = g_tuning.tail == 1 && n > TRI_TAIL_MAX && n <= PK_NMAX;
-    if (go_flag && !packed) return BASD_EUNSUPPORTED;       // only the one-kernel factorisation can be queued early
-    const int j_stop = !tail ? n - 1 : (packed ? 0 : (n > TRI_TAIL_MAX ? n - TRI_TAIL_MAX : 0));
-    if (j_stop > 0) {
-        const bool vec = (n & 3) == 0 && (a_batch_stride & 3) == 0 && (((uintptr_t)a) & 15) == 0;
-        const int P = tridiag_members(n, batch);
-        int batch_pad = P > 1 ? (batch + 7) & ~7 : batch;
-        if (g_tuning.pad >= 0) batch_pad = batch + g_tuning.pad;
+    float* pend = (float*)((char*)work + p.ws.pend_off);
+    int* err = (int*)((char*)work + p.ws.status_off);
+    if (p.front == plan::kFrontShared) {
         // 20-bit launch nonce in the granule tags (12 bits of step below it: n <= 4096), never 0: a zero-filled
         // granule of fresh memory must not look like step 0 of any launch.  The counter only has to differ between
         // launches that can see each other's granules (same recycled buffer), not to be unique for ever.
         static std::atomic<unsigned> launches{0};
         const unsigned tag_base = (1u + launches.fetch_add(1, std::memory_order_relaxed) % 0xFFFFFu) << 12;
-        const size_t lds = sizeof(float) * 9 * (size_t)n;
         // Always 1024 threads per member.  A member with one 32-row block keeps only four waves busy in the pass and
         // 512 threads made its barriers cheaper (n = 384, 12 members: 1.55 ms against 1.63) -- but round 3 found every
         // workgroup size BELOW 1024 (256, 512, 768; 4, 6 or 12 members) delivering wrong factorisations (status words
@@ -2203,13 +2024,13 @@ static int tridiag_impl(float* a, long a_batch_stride, int n, int batch, float* 
         // the same 48 KB: clean); the fp32 MFMA kernels, the LDS / VALU-bound Jacobi and HBM streams as neighbours: clean.
         // Cause not found; the smaller sizes stay reachable through basd_tridiag_tuning(threads) for whoever wants to hunt
         // it, production never takes them.
-        int threads = 1024;
-        if (g_tuning.threads > 0) threads = g_tuning.threads;
-        const int lag = g_tuning.lag;
-        if (vec && (n & 7) == 0) tridiag_kernel<true, true><<<P * batch_pad, threads, lds, stream>>>(a, a_batch_stride, n, batch, batch_pad, P, d, e, tau, vh, xg, err, tag_base, lag, j_stop, pend);
-        else if (vec) tridiag_kernel<true, false><<<P * batch_pad, threads, lds, stream>>>(a, a_batch_stride, n, batch, batch_pad, P, d, e, tau, vh, xg, err, tag_base, lag, j_stop, pend);
-        else tridiag_kernel<false, false><<<P * batch_pad, threads, lds, stream>>>(a, a_batch_stride, n, batch, batch_pad, P, d, e, tau, vh, xg, err, tag_base, lag, j_stop, pend);
-    } else {
+        const int P = p.members, batch_pad = p.batch_pad, threads = p.threads, lag = g_tuning.lag, j_stop = p.j_stop;
+        const size_t lds = (size_t)p.lds;
+        if (p.variant == plan::kVecFull) tridiag_kernel<true, true><<<p.grid, threads, lds, stream>>>(a, a_batch_stride, n, batch, batch_pad, P, d, e, tau, vh, xg, err, tag_base, lag, j_stop, pend);
+        else if (p.variant == plan::kVec) tridiag_kernel<true, false><<<p.grid, threads, lds, stream>>>(a, a_batch_stride, n, batch, batch_pad, P, d, e, tau, vh, xg, err, tag_base, lag, j_stop, pend);
+        else tridiag_kernel<false, false><<<p.grid, threads, lds, stream>>>(a, a_batch_stride, n, batch, batch_pad, P, d, e, tau, vh, xg, err, tag_base, lag, j_stop, pend);
+    }
+    if (p.memset_status) {
         hipError_t me = hipMemsetAsync(err, 0, 32, stream);        // no shared stage: the status words stay clean
         if (me != hipSuccess) return (int)me;
     }
@@ -2220,18 +2041,14 @@ static int tridiag_impl(float* a, long a_batch_stride, int n, int batch, float* 
         if (ee != hipSuccess) return (int)ee;
     }
     rk.status = err;
-    const bool fused_rank = tail && rk.rank_out && 2 * n <= 8 * TRI_TAIL_MAX;
-    if (tail) {
-        MpRankOut in_tail = rk;
-        if (!fused_rank) in_tail.rank_out = nullptr;
-        if (packed)
-            tridiag_packed_kernel<<<batch, 64 * PK_WAVES, 0, stream>>>(a, a_batch_stride, n, d, e, tau, vh, in_tail, g_pk_clocks, go_flag, go_value, go_budget);
-        else if (g_tuning.tail == 2)      // the four-barrier form (16 waves): kept for the tests that compare the two
-            tridiag_tail_kernel<16, 16, 4><<<batch, 1024, 0, stream>>>(a, a_batch_stride, n, j_stop, j_stop > 0 ? pend : nullptr, d, e, tau, vh, in_tail);
-        else
-            tridiag_tail2_kernel<<<batch, 512, 0, stream>>>(a, a_batch_stride, n, j_stop, j_stop > 0 ? pend : nullptr, d, e, tau, vh, in_tail);
-    }
-    if (rk.rank_out && !fused_rank)
+    MpRankOut in_back = rk;
+    if (p.ranks != plan::kRanksInBack) in_back.rank_out = nullptr;
+    const float* pend_in = p.j_stop > 0 ? pend : nullptr;
+    if (p.back == plan::kBackPacked)
+        tridiag_packed_kernel<<<batch, 64 * PK_WAVES, 0, stream>>>(a, a_batch_stride, n, d, e, tau, vh, in_back, g_pk_clocks, go_flag, go_value, go_budget);
+    else if (p.back == plan::kBackTail2)
+        tridiag_tail2_kernel<<<batch, 512, 0, stream>>>(a, a_batch_stride, n, p.j_stop, pend_in, d, e, tau, vh, in_back);
+    if (p.ranks == plan::kRanksSeparate)
         tridiag_mp_rank_kernel<<<rk.count, 1024, 0, stream>>>(d, e, n, rk.factor, rk.cap, rk.rank_out, nullptr, rk.host_mirror ? err : nullptr, rk.host_mirror);
     BASD_RETURN_LAST();
 }
@@ -2248,7 +2065,6 @@ int basd_tridiag_ranked(float* a, long a_batch_stride, int n, int batch, float* 
                         void* work, int rank_count, double factor, int cap, int* rank_out, int* host_mirror,
                         void* mid_event, hipStream_t stream) {
     BASD_CHECK_ARG(rank_out && rank_count > 0 && rank_count <= batch);
-    if (n > 8192) return BASD_EUNSUPPORTED;
     return tridiag_impl(a, a_batch_stride, n, batch, d, e, tau, vh, work,
                         MpRankOut{rank_out, host_mirror, nullptr, factor, cap, rank_count}, stream,
                         (hipEvent_t)mid_event);
@@ -2298,22 +2114,38 @@ int basd_tridiag_eigenvalues_leading(const float* d, const float* e, int n, int 
     BASD_RETURN_LAST();
 }
 
+// backtransform_kernel over the k rows of x, four per workgroup.  Callers reject an order without a route beforehand.
+static void launch_backtransform(const float* tau, const float* vh, int n, int k, int batch, const float* x, float* out,
+                                 int k_stride, bool transpose, hipStream_t stream) {
+    const dim3 grid((k + 3) / 4, batch);
+#define BASD_BACKTRANSFORM(E)                                                                                    \
+    case E:                                                                                                       \
+        if (transpose) backtransform_kernel<E, true><<<grid, 256, 0, stream>>>(vh, tau, n, k, x, out, k_stride);  \
+        else backtransform_kernel<E, false><<<grid, 256, 0, stream>>>(vh, tau, n, k, x, out, k_stride);           \
+        break
+    switch (plan::backtransform_epl(n)) {
+        BASD_BACKTRANSFORM(3);
+        BASD_BACKTRANSFORM(6);
+        BASD_BACKTRANSFORM(12);
+        BASD_BACKTRANSFORM(16);
+    }
+#undef BASD_BACKTRANSFORM
+}
+
+// The LDS tile of tridiag_invit_kernel / tridiag_shifted_solve_kernel at order n, opted in where it passes 48 KB
+// (vpw == 0, nothing fits: no bytes, nothing set).
+static plan::SolveTile solve_tile_for(const void* kernel, int n) {
+    const plan::SolveTile t = plan::solve_tile(n);
+    if (t.lds > 48 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds);
+    return t;
+}
+
 // out (batch, k_stride, n) rows = Q x or Q^T x for the rows of x (batch, k, n); Q = H_0 ... H_{n-2} of basd_tridiag.
 int basd_tridiag_apply_q(const float* tau, const float* vh, int n, int k, int batch, const float* x, float* out,
                          int k_stride, int transpose, hipStream_t stream) {
     BASD_CHECK_ARG(tau && vh && x && out && n > 1 && k > 0 && batch > 0 && k_stride >= k);
-    const dim3 grid((k + 3) / 4, batch);
-#define BASD_APPLY_Q(E)                                                                                          \
-    do {                                                                                                          \
-        if (transpose) backtransform_kernel<E, true><<<grid, 256, 0, stream>>>(vh, tau, n, k, x, out, k_stride);  \
-        else backtransform_kernel<E, false><<<grid, 256, 0, stream>>>(vh, tau, n, k, x, out, k_stride);           \
-    } while (0)
-    if (n <= 192) BASD_APPLY_Q(3);
-    else if (n <= 384) BASD_APPLY_Q(6);
-    else if (n <= 768) BASD_APPLY_Q(12);
-    else if (n <= 1024) BASD_APPLY_Q(16);
-    else return BASD_EUNSUPPORTED;
-#undef BASD_APPLY_Q
+    if (!plan::backtransform_epl(n)) return BASD_EUNSUPPORTED;
+    launch_backtransform(tau, vh, n, k, batch, x, out, k_stride, transpose != 0, stream);
     BASD_RETURN_LAST();
 }
 
@@ -2321,13 +2153,9 @@ int basd_tridiag_apply_q(const float* tau, const float* vh, int n, int k, int ba
 int basd_tridiag_shifted_solve(const float* d, const float* e, const float* shifts, int shift_stride, int n, int k,
                                int batch, const float* rhs, float* x, hipStream_t stream) {
     BASD_CHECK_ARG(d && e && shifts && rhs && x && n > 1 && k > 0 && batch > 0 && shift_stride >= k);
-    int vpw = (int)((144 * 1024) / (6 * sizeof(float) * (size_t)n));
-    if (vpw > 64) vpw = 64;
-    if (vpw < 1) return BASD_EUNSUPPORTED;
-    const size_t lds_a = sizeof(float) * 6 * (size_t)n * vpw;
-    if (lds_a > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)tridiag_shifted_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
-    tridiag_shifted_solve_kernel<<<dim3((k + vpw - 1) / vpw, batch), 64, lds_a, stream>>>(d, e, shifts, shift_stride, n, k, vpw, rhs, x);
+    const plan::SolveTile t = solve_tile_for((const void*)tridiag_shifted_solve_kernel, n);
+    if (t.vpw < 1) return BASD_EUNSUPPORTED;
+    tridiag_shifted_solve_kernel<<<dim3((k + t.vpw - 1) / t.vpw, batch), 64, t.lds, stream>>>(d, e, shifts, shift_stride, n, k, t.vpw, rhs, x);
     BASD_RETURN_LAST();
 }
 
@@ -2367,26 +2195,14 @@ int basd_tridiag_eigenvectors(const float* d, const float* e, const float* tau, 
                               hipStream_t stream) {
     BASD_CHECK_ARG(d && e && tau && vh && vals_desc && z && vecs && n > 1 && k > 0 && k <= n && batch > 0);
     BASD_CHECK_ARG(k_stride >= k && k <= 1024);
-    int vpw = (int)((144 * 1024) / (6 * sizeof(float) * (size_t)n));
-    if (vpw > 64) vpw = 64;
-    if (vpw < 1) return BASD_EUNSUPPORTED;
-    const size_t lds_a = sizeof(float) * 6 * (size_t)n * vpw;
-    if (lds_a > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)tridiag_invit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
-    tridiag_invit_kernel<<<dim3((k + vpw - 1) / vpw, batch), 64, lds_a, stream>>>(d, e, vals_desc, n, k, vpw, z);
-    {
-        if (n > 1024) return BASD_EUNSUPPORTED;
-        const size_t lds_c = sizeof(float) * (((size_t)k + 3) / 4 * 4 + 16 * (size_t)n);
-        if (lds_c > 48 * 1024)
-            (void)hipFuncSetAttribute((const void*)cluster_orth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-        cluster_orth_kernel<<<batch, 1024, lds_c, stream>>>(d, e, vals_desc, n, k, z);
-    }
-    const dim3 grid((k + 3) / 4, batch);
-    if (n <= 192) backtransform_kernel<3><<<grid, 256, 0, stream>>>(vh, tau, n, k, z, vecs, k_stride);
-    else if (n <= 384) backtransform_kernel<6><<<grid, 256, 0, stream>>>(vh, tau, n, k, z, vecs, k_stride);
-    else if (n <= 768) backtransform_kernel<12><<<grid, 256, 0, stream>>>(vh, tau, n, k, z, vecs, k_stride);
-    else if (n <= 1024) backtransform_kernel<16><<<grid, 256, 0, stream>>>(vh, tau, n, k, z, vecs, k_stride);
-    else return BASD_EUNSUPPORTED;
+    if (!plan::backtransform_epl(n)) return BASD_EUNSUPPORTED;      // before anything is queued; the tile holds >= 6 vectors here
+    const plan::SolveTile t = solve_tile_for((const void*)tridiag_invit_kernel, n);
+    tridiag_invit_kernel<<<dim3((k + t.vpw - 1) / t.vpw, batch), 64, t.lds, stream>>>(d, e, vals_desc, n, k, t.vpw, z);
+    const size_t lds_c = sizeof(float) * (((size_t)k + 3) / 4 * 4 + 16 * (size_t)n);
+    if (lds_c > 48 * 1024)
+        (void)hipFuncSetAttribute((const void*)cluster_orth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
+    cluster_orth_kernel<<<batch, 1024, lds_c, stream>>>(d, e, vals_desc, n, k, z);
+    launch_backtransform(tau, vh, n, k, batch, z, vecs, k_stride, false, stream);
     BASD_RETURN_LAST();
 }
 
