@@ -655,6 +655,25 @@ int basd_procrustes_plan_query(const BasdProcrustesArgs* args, long* out20);
  * are 0, every other field is what basd_procrustes_plan_query answers for the same argument block. */
 int basd_procrustes_forward_cached(const BasdProcrustesArgs* args, hipStream_t stream);
 int basd_procrustes_plan_query_cached(const BasdProcrustesArgs* args, long* out20);
+/* The other half: those three arrays computed BY THEMSELVES, for any set of images, without a student.
+ * basd_procrustes_teacher_side queues the part of basd_procrustes_forward_fused ahead of its student projection and then
+ * its teacher Gram, through the same code (fused.hip: teacher_weights_and_centring, teacher_gram): basd_token_weights,
+ * the centring route of the plan (L == 1, G == 1: basd_teacher_center), and basd_gram_f64_split (g_slabs set and
+ * g_splits > 1; g_slabs: g_splits * B*n*n doubles) or basd_gram_f64.  No projection, Cholesky, SVD or finish.
+ *   read:    tok_ptrs, t_*, attn_ptrs, a_*, mix (one float, 1), L, G, B, n_s, n_t, d_t, H, A, has_cls, n_a, n, the
+ *            taps (atap*, tap0 / tap1 / lam, g0 / g1 / glam), raw (nullable), g_slabs, g_splits
+ *   written: omega (B, n_s), omega_t (B, n), scratch mu_t (B, d_t) and tc (B, n, d_t), and g_all, which for THIS call
+ *            is the (B, n, n) fp64 teacher Gram itself (there are no student Grams ahead of it)
+ *   not read: E, d_s and every student field; every array behind the Grams.
+ * Row b of the three outputs depends on image b and on g_splits alone -- not on B, on b or on the other images: the
+ * token weights and the centring work per sample, and the split Gram folds a matrix's g_splits slabs in a fixed order.
+ * With the g_splits of an uncached call the rows are bit for bit those that call leaves in its teacher slot.
+ * L != 1, G != 1, a core grid past the centring kernel's LDS (n > ~580) or past the Gram's: BASD_EUNSUPPORTED before
+ * anything is queued.  basd_procrustes_plan_query_teacher_side answers for it from the same predicates: fields 0, 4,
+ * 13, 14 and 16 are those of basd_procrustes_plan_query for the same teacher arguments, every student-side field is 0
+ * ("none"), and the status is BASD_OK or BASD_EUNSUPPORTED by the teacher-side stages alone. */
+int basd_procrustes_teacher_side(const BasdProcrustesArgs* args, hipStream_t stream);
+int basd_procrustes_plan_query_teacher_side(const BasdProcrustesArgs* args, long* out20);
 /* The cache of those arrays, one row per dataset image: cache_g (capacity, n, n) fp64, cache_omega (capacity, n_s),
  * cache_omega_t (capacity, n), all dense.  One launch each:
  *   basd_teacher_cache_store scatters the B rows a call has just produced (g (B, n, n), omega (B, n_s), omega_t (B, n),

@@ -88,6 +88,8 @@ SIGNATURES = {
     "basd_procrustes_plan_query": [vp, vp],
     "basd_procrustes_forward_cached": [vp, vp],
     "basd_procrustes_plan_query_cached": [vp, vp],
+    "basd_procrustes_teacher_side": [vp, vp],
+    "basd_procrustes_plan_query_teacher_side": [vp, vp],
     "basd_teacher_cache_store": [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp],
     "basd_teacher_cache_load": [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp],
     "basd_procrustes_tuning": [i32],

@@ -1552,6 +1552,25 @@ class BASDLoss(nn.Module):
             raise ValueError(side)
         return side
 
+    def teacher_side(self, teacher_tokens: dict[int, torch.Tensor], teacher_attns: dict[int, torch.Tensor], *,
+                     as_batch: int | None = None) -> "ops.TeacherSide":
+        """The teacher side of a set of images by itself, without a student: what ``last_teacher_side()`` would hand
+        out after a ``forward`` on these teacher tensors, as FRESH tensors (``ops.procrustes_teacher_side``) that stay
+        valid -- for ``TeacherCache.store`` ahead of training (``Trainer.fill_teacher_cache``) or for the missing rows of
+        a partly cached batch.  ``teacher_tokens`` / ``teacher_attns``: the dicts ``extract_intermediates`` returns, ONE
+        layer (``ValueError`` otherwise: with more the mixing weights depend on the student).  ``as_batch``: the batch
+        size of the training step (``None``: this call's); with it a row has the bits the uncached step would store for
+        the same teacher tokens, whatever else is in this call.  The selector and ``last_components`` are not touched."""
+        if len(teacher_tokens) != 1 or len(teacher_attns) != 1:
+            raise ValueError(_MULTI_LAYER_TEACHER)
+        (key, tokens), = teacher_tokens.items()
+        if key not in teacher_attns:
+            raise ValueError(f"teacher attention has no layer {key!r} (got {sorted(teacher_attns)})")
+        if tokens.requires_grad or teacher_attns[key].requires_grad:
+            raise ValueError(_TEACHER_REQUIRES_GRAD)
+        return ops.procrustes_teacher_side(tokens, teacher_attns[key], bool(self.teacher_has_cls_token),
+                                           self.num_student_tokens, as_batch=as_batch)
+
     def forward_cached(self, student_output: torch.Tensor, targets: torch.Tensor,
                        student_intermediates: dict[int, torch.Tensor], teacher_side) -> torch.Tensor:
         """``forward`` for ONE teacher layer without the teacher: ``teacher_side`` is what ``last_teacher_side()`` gave

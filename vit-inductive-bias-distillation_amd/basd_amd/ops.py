@@ -715,6 +715,33 @@ def _check_common_layout(tensors: list[torch.Tensor], what: str) -> list[torch.T
     return out
 
 
+def teacher_gram_splits(GB: int, d_t: int) -> int:
+    """Over how many workgroups per matrix the contraction of the teacher Gram is split (``g_splits`` of
+    ``BasdProcrustesArgs``) when ``GB`` teacher Grams of feature width ``d_t`` are formed in one call: few Grams with a
+    long feature axis leave most CUs idle unsplit.  The split count decides the order in which a Gram's partial sums
+    are folded, so rows computed apart from their step (``procrustes_teacher_side``) must be formed with the count of
+    that step's batch."""
+    if GB < 1024 and d_t >= 512:
+        return max(1, min(1024 // GB, d_t // 256, 16))
+    return 1
+
+
+def _plan_taps(n_s: int, n_t: int, n_a: int, dev: torch.device) -> tuple:
+    """(student-side (transposed) taps, teacher-side gather taps, attention taps) of a call: ``Taps`` or ``None``."""
+    return (taps(n_t, n_s, dev) if n_t < n_s else None, taps(n_t, n_s, dev) if n_t > n_s else None,
+            taps(n_a, n_s, dev))
+
+
+def _set_taps(a, tp: Taps | None, gt: Taps | None, atp: Taps | None) -> None:
+    if atp:
+        a.atap0, a.atap1, a.alam = atp.tap0.data_ptr(), atp.tap1.data_ptr(), atp.lam.data_ptr()
+    if tp:
+        a.tap0, a.tap1, a.lam = tp.tap0.data_ptr(), tp.tap1.data_ptr(), tp.lam.data_ptr()
+        a.range0, a.range1 = tp.range0.data_ptr(), tp.range1.data_ptr()
+    if gt:
+        a.g0, a.g1, a.glam = gt.tap0.data_ptr(), gt.tap1.data_ptr(), gt.lam.data_ptr()
+
+
 class _ProcrustesPlan:
     """Persistent scratch + a pre-filled ``BasdProcrustesArgs`` for one (shapes, layouts, options, stream) key.
 
@@ -748,9 +775,7 @@ class _ProcrustesPlan:
         n_a = A - (1 if has_cls else 0)
         n = min(n_s, n_t)
         self.n, self.n_a = n, n_a
-        self.tp = taps(n_t, n_s, dev) if n_t < n_s else None                 # student-side (transposed) taps
-        self.gt = taps(n_t, n_s, dev) if n_t > n_s else None                 # teacher-side gather taps
-        self.atp = taps(n_a, n_s, dev)
+        self.tp, self.gt, self.atp = _plan_taps(n_s, n_t, n_a, dev)
         G = self.G = 1 if L == 1 else E          # softmax over one layer is exactly 1: the teacher side is shared
         f32 = dict(device=dev, dtype=torch.float32)
         EB, GB = E * B, G * B
@@ -762,10 +787,7 @@ class _ProcrustesPlan:
         self.kept_padded = [(c + 63) // 64 * 64 for c in self.kept_sizes]
         self.kept_total = sum(self.kept_padded)
         # ---- scratch
-        g_splits = 1
-        if not given and GB < 1024 and d_t >= 512:           # few teacher Grams with a long feature axis: split the contraction
-            g_splits = max(1, min(1024 // GB, d_t // 256, 16))
-        self.g_splits = g_splits
+        g_splits = self.g_splits = 1 if given else teacher_gram_splits(GB, d_t)
         self.g_all = torch.empty((EB + GB + (g_splits * GB if g_splits > 1 else 0), n, n), device=dev, dtype=torch.float64)
         self.l_all = torch.empty((EB + GB, n, n), device=dev, dtype=torch.float64)
         self.W = torch.empty((EB, n, 2 * n), **f32)        # memory == column-major (2n x n)
@@ -817,13 +839,7 @@ class _ProcrustesPlan:
         padded = [(c + 63) // 64 * 64 for c in sizes]
         self.omega_t, self.mu_t, self.tr_part, self.sigma = (
             piece[:c] for piece, c in zip(torch.split(torch.empty((sum(padded),), **f32), padded), sizes))
-        if self.atp:
-            a.atap0, a.atap1, a.alam = self.atp.tap0.data_ptr(), self.atp.tap1.data_ptr(), self.atp.lam.data_ptr()
-        if self.tp:
-            a.tap0, a.tap1, a.lam = self.tp.tap0.data_ptr(), self.tp.tap1.data_ptr(), self.tp.lam.data_ptr()
-            a.range0, a.range1 = self.tp.range0.data_ptr(), self.tp.range1.data_ptr()
-        if self.gt:
-            a.g0, a.g1, a.glam = self.gt.tap0.data_ptr(), self.gt.tap1.data_ptr(), self.gt.lam.data_ptr()
+        _set_taps(a, self.tp, self.gt, self.atp)
         a.omega_t, a.mu_t, a.tc, a.tr_part = (self.omega_t.data_ptr(), self.mu_t.data_ptr(), self.tc.data_ptr(),
                                               self.tr_part.data_ptr())
         a.g_all, a.l_all, a.W = self.g_all.data_ptr(), self.l_all.data_ptr(), self.W.data_ptr()
@@ -1026,6 +1042,65 @@ def procrustes_forward_cached(students: list[torch.Tensor], teacher_side, *, nee
     sweeps = plan.sweeps.clone() if plan.sweeps is not None else None
     return ProcrustesContext(omega, mu_s, a_prime, k_prime, terms[0], terms[1], terms[2], terms[3], sweeps, None,
                              dx, uw, side)
+
+
+def procrustes_teacher_side(teacher: torch.Tensor, attn: torch.Tensor, has_cls: bool, n_s: int, *,
+                            as_batch: int | None = None) -> TeacherSide:
+    """The teacher side of ONE teacher layer by itself (basd_procrustes_teacher_side): what ``procrustes_forward`` leaves
+    as ``ctx.teacher_side`` for these teacher tokens, without a student.  ``teacher``: (B, n_t, d_t), fp32 or bf16, any
+    strides the uncached call takes (a CNN map arrives as a transposed view); ``attn``: (B, H, A, A); ``n_s``: the
+    student's token count.  Returns FRESH tensors ``g`` (B, n, n) fp64, ``omega`` (B, n_s) and ``omega_t`` (B, n) fp32,
+    ``n = min(n_s, n_t)``: no views of shared scratch, they stay valid across later calls.
+
+    The launches are the uncached call's own -- token weights, centring, fp64 Gram -- so row ``i`` is a function of
+    image ``i`` and of the Gram's split count alone: not of the other images, of its position or of ``B``.
+    ``as_batch``: the batch size of the step whose rows these must equal bit for bit; it fixes the split count
+    (``teacher_gram_splits(as_batch, d_t)``).  ``None``: ``B``."""
+    import ctypes
+    if not (isinstance(teacher, torch.Tensor) and teacher.dim() == 3 and isinstance(attn, torch.Tensor)
+            and attn.dim() == 4 and attn.shape[0] == teacher.shape[0] and attn.shape[2] == attn.shape[3]):
+        raise ValueError("procrustes_teacher_side takes ONE teacher layer: tokens (B, n_t, d_t) and attention "
+                         f"(B, H, A, A); got {tuple(getattr(teacher, 'shape', ()))} and {tuple(getattr(attn, 'shape', ()))}")
+    if isinstance(n_s, bool) or not isinstance(n_s, int) or n_s <= 0:
+        raise ValueError(f"n_s must be an int > 0 (got {n_s!r})")
+    if as_batch is not None and (isinstance(as_batch, bool) or not isinstance(as_batch, int) or as_batch <= 0):
+        raise ValueError(f"as_batch must be None or an int > 0 (got {as_batch!r})")
+    if teacher.requires_grad or attn.requires_grad:
+        raise ValueError("procrustes_teacher_side has no backward: the teacher is frozen (a tensor requires grad)")
+    teacher, attn = as_supported(teacher), as_supported(attn)
+    _require_cuda(teacher, attn)
+    dev = teacher.device
+    B, n_t, d_t = teacher.shape
+    H, A = attn.shape[1], attn.shape[2]
+    n_a = A - (1 if has_cls else 0)
+    n = min(n_s, n_t)
+    if B == 0 or n_a <= 0:
+        raise ValueError(f"empty teacher layer: tokens {tuple(teacher.shape)}, attention {tuple(attn.shape)}")
+    g_splits = teacher_gram_splits(B if as_batch is None else as_batch, d_t)
+    f32 = dict(device=dev, dtype=torch.float32)
+    g = torch.empty((B, n, n), device=dev, dtype=torch.float64)
+    omega, omega_t = torch.empty((B, n_s), **f32), torch.empty((B, n), **f32)
+    # scratch of this call alone, handed back to the allocator behind its launches on this stream
+    mu_t, tc = torch.empty((B, d_t), **f32), torch.empty((B, n, d_t), **f32)
+    slabs = torch.empty((g_splits * B, n, n), device=dev, dtype=torch.float64) if g_splits > 1 else None
+    tabs = _plan_taps(n_s, n_t, n_a, dev)
+
+    a = _lib.ProcrustesArgs()
+    a.L = a.G = 1
+    a.B, a.n_s, a.n_t, a.d_t, a.H, a.A, a.has_cls, a.n_a, a.n = B, n_s, n_t, d_t, H, A, int(bool(has_cls)), n_a, n
+    a.tok_ptrs, a.attn_ptrs = _ptr_table([teacher]).data_ptr(), _ptr_table([attn]).data_ptr()
+    a.t_dtype, a.t_sb, a.t_sn, a.t_sd = (_dtype_code(teacher), *teacher.stride())
+    a.a_dtype = _dtype_code(attn)
+    a.a_sb, a.a_sh, a.a_sq, a.a_sk = attn.stride()
+    a.mix = _device_consts((1.0,), torch.float32, dev).data_ptr()
+    _set_taps(a, *tabs)
+    a.omega, a.omega_t, a.mu_t, a.tc, a.g_all = (omega.data_ptr(), omega_t.data_ptr(), mu_t.data_ptr(), tc.data_ptr(),
+                                                 g.data_ptr())
+    a.g_splits, a.g_slabs = g_splits, _ptr(slabs)
+    gpu_mark("teacher_side_begin")
+    _lib.call("basd_procrustes_teacher_side", ctypes.addressof(a), _stream())
+    gpu_mark("teacher_side_end")
+    return TeacherSide(g, omega, omega_t)
 
 
 def scale_unless_one(x: torch.Tensor, num: torch.Tensor, den: torch.Tensor | None = None) -> None:

@@ -79,7 +79,7 @@ class TeacherCache:
     leave the same bytes.  ``load(index)`` checks ON THE HOST that every row was stored -- ``KeyError`` naming the first
     that was not -- and returns a ``CachedTeacherSide``; a repeated index is legal.  Both run on the current stream;
     rows are visible to loads queued behind their store on that stream (or ordered behind it by an event).
-    ``has(index)``: whether all those rows are filled, plain Python.  ``clear()`` empties the bitmap (the device
+    ``has(index)``: whether all those rows are filled, plain Python; ``filled(index)``: which of them.  ``clear()`` empties the bitmap (the device
     memory is kept).  Arguments are checked before anything is queued: the index (1-D int64, within ``[0, capacity)``,
     as long as the batch), shapes and dtypes (``ValueError``), then the devices -- CPU tensors, or a cache made on a
     CPU device, raise the package's "no CPU fallback" ``RuntimeError`` in ``store`` and ``load``.
@@ -138,6 +138,10 @@ class TeacherCache:
     def has(self, index) -> bool:
         """Whether every row of ``index`` has been stored (host only; give a host tensor)."""
         return bool(self._filled[self._host_index(index)].all())
+
+    def filled(self, index) -> torch.Tensor:
+        """Per entry of ``index`` whether its row has been stored: a host bool tensor (host only; give a host tensor)."""
+        return torch.from_numpy(self._filled[self._host_index(index)])
 
     def store(self, index, teacher_side, *, device_index=None) -> None:
         """``device_index``: the same indices already on the device (saves the upload)."""

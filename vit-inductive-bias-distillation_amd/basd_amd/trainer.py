@@ -68,6 +68,27 @@ def shard_loader(dataset, batch_size: int, *, shuffle: bool = True, seed: int = 
                                        shuffle=shuffle and sampler is None, drop_last=True, **kw)
 
 
+_TOKEN_FORMAT_WHY = ("a token-format teacher hands over every block, and with more than one teacher layer the mixing "
+                     "weights depend on the student, so the mixed teacher's Gram is not a property of the image")
+
+
+def _teacher_rows(filled, k: int):
+    """Which batch positions the teacher sees in a step with ``teacher_partial=k``.  ``filled``: per batch position,
+    whether the image's cache row has been stored (anything ``torch.as_tensor`` takes as bools).  The positions that are
+    not filled, in batch order, then -- padding to the next multiple of ``k`` -- the first filled positions in batch
+    order: the teacher then meets at most ``B / k`` batch shapes instead of ``B``.  An empty tensor: nothing is missing
+    (a cached step).  ``None``: everything is missing or the padded count reaches ``B`` -- the ordinary uncached step."""
+    filled = torch.as_tensor(filled, dtype=torch.bool).reshape(-1)
+    B = filled.numel()
+    missing = torch.nonzero(~filled).reshape(-1)
+    if missing.numel() == 0:
+        return missing
+    padded = -(-missing.numel() // k) * k
+    if padded >= B:
+        return None
+    return torch.cat([missing, torch.nonzero(filled).reshape(-1)[:padded - missing.numel()]])
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # the trainer
 # ----------------------------------------------------------------------------------------------------------------
@@ -144,14 +165,28 @@ class Trainer:
     and their order do not change (the clean view draws nothing).  The cache is valid for one teacher, one clean
     transform, one set of clean statistics and one autocast dtype, and never invalidates itself (``TeacherCache``);
     ``evaluate`` does not use it and checkpoints do not contain it.  With more than one rank each rank fills what its
-    sampler shows it."""
+    sampler shows it -- unless every rank runs ``fill_teacher_cache`` over the whole dataset once before ``train``: then
+    every step of every rank is cached from the first epoch on, and nothing is exchanged between ranks.
+    ``teacher_partial``: an int >= 0 (it needs ``teacher_cache``).  0, the default: a batch with any unseen image takes the
+    uncached step.  ``k > 0``: ``prepare_batch`` finds the positions whose rows are not filled (on the host, from the
+    bitmap) and pads them to the next multiple of ``k`` with the first filled positions (``_teacher_rows``; the padding
+    keeps the teacher to ``B / k`` batch shapes, each new convolution shape costing a search in the vendor library).  If
+    that reaches ``B`` the step is the uncached one.  Otherwise the teacher runs on those rows of the clean view only,
+    ``BASDLoss.teacher_side(..., as_batch=B)`` makes their rows, the genuinely missing ones are stored (a stored row is
+    never written again), and the step is the cached one (``load`` -> ``forward_cached``; like it, it does not run the
+    selector).  The draws and their order do not change.  ``prepared`` then also carries ``teacher_rows``: the positions
+    the teacher will see (empty for a cached step), or ``None`` for an uncached step.
+    One caveat for both: a vendor convolution may pick another algorithm at another batch size, so a row made at batch
+    ``m`` (a fill pass, a partly cached step) can differ in its last bits from the row an uncached step at batch ``B``
+    would have stored.  That is the teacher's property, not the loss's: given equal teacher tokens the rows are equal
+    bit for bit."""
 
     def __init__(self, student_model: nn.Module, config, teacher, *, student_info: dict, loss_cls=None,
                  autocast_dtype=None, mixup=True, optimizer: str = "adamw", image_stats=None, mix_dtype=None,
                  attn_capture: str = "torch", trivial_augment: bool = False, flip_p: float = 0.5,
                  resize_crop: bool = False, jpeg_decode=False, png_decode: bool = False, max_grad_norm=None,
                  skip_nonfinite: bool = False, prefetch: int = 0, resize_interpolation="bilinear",
-                 check_factorisations: bool = False, teacher_cache=None) -> None:
+                 check_factorisations: bool = False, teacher_cache=None, teacher_partial: int = 0) -> None:
         if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
             raise ValueError(f"prefetch must be an int >= 0 (got {prefetch!r})")
         self._guarded = max_grad_norm is not None or bool(skip_nonfinite)
@@ -162,11 +197,15 @@ class Trainer:
                     isinstance(teacher_cache, bool) or not isinstance(teacher_cache, int) or teacher_cache <= 0):
                 raise ValueError(f"teacher_cache must be None, a TeacherCache or a capacity > 0 (got {teacher_cache!r})")
             if teacher.feature_format == "token":
-                raise ValueError("teacher_cache needs a teacher with ONE extracted layer (feature_format != 'token'): a "
-                                 "token-format teacher hands over every block, and with more than one teacher layer "
-                                 "the mixing weights depend on the student, so the mixed teacher's Gram is not a "
-                                 f"property of the image; got feature_format={teacher.feature_format!r}")
+                raise ValueError("teacher_cache needs a teacher with ONE extracted layer (feature_format != 'token'): "
+                                 f"{_TOKEN_FORMAT_WHY}; got feature_format={teacher.feature_format!r}")
         self.teacher_cache = teacher_cache
+        if isinstance(teacher_partial, bool) or not isinstance(teacher_partial, int) or teacher_partial < 0:
+            raise ValueError(f"teacher_partial must be an int >= 0 (got {teacher_partial!r})")
+        if teacher_partial and teacher_cache is None:
+            raise ValueError("teacher_partial runs the teacher on the images a teacher_cache lacks: it needs "
+                             f"teacher_cache; got teacher_cache=None and teacher_partial={teacher_partial!r}")
+        self.teacher_partial = teacher_partial
         if self._guarded and optimizer != "schedulefree":
             raise ValueError("max_grad_norm and skip_nonfinite are part of AdamWScheduleFree's update: they need "
                              f"optimizer='schedulefree'; got optimizer={optimizer!r}")
@@ -286,14 +325,33 @@ class Trainer:
                         f"{'given' if self.image_stats is not None else None}{got}")
 
     # -- one batch: the body of the reference's _train_epoch loop (trainer.py:133-164)
-    def prepare_views(self, batch: dict, *, want_clean: bool = True):
+    def prepare_views(self, batch: dict, *, want_clean: bool = True, clean_rows=None):
         """``(clean, augmented)`` of a batch on the device.  With ``resize_crop`` both are made from the batch's
         ``"images"`` by one launch (uint8, ``(B, C, S, S)``); without, they are the batch's own entries.
-        ``want_clean=False`` (the teacher side of every image is cached): ``clean`` is ``None``, not uploaded or made."""
+        ``want_clean=False`` (the teacher side of every image is cached): ``clean`` is ``None``, not uploaded or made.
+        ``clean_rows`` (a host int64 vector, ``teacher_partial``): ``clean`` holds those batch positions only -- a host
+        tensor is selected on the host, ahead of the upload."""
         dev = self.device
         if self._resizer is None:
-            clean = batch["clean"].to(dev, non_blocking=True) if want_clean else None
+            clean = self._select_rows(batch["clean"], clean_rows).to(dev, non_blocking=True) if want_clean else None
             return clean, batch["augmented"].to(dev, non_blocking=True)
+        images = self._decoded_images(batch)
+        if not want_clean:
+            views = self._resizer(images.to(dev, non_blocking=True), batch.get("crop_params"), views=("augmented",))
+            return None, views["augmented"]
+        views = self._resizer(images.to(dev, non_blocking=True), batch.get("crop_params"))
+        return self._select_rows(views["clean"], clean_rows), views["augmented"]
+
+    @staticmethod
+    def _select_rows(images: torch.Tensor, rows) -> torch.Tensor:
+        if rows is None:
+            return images
+        return images[rows.to(images.device, non_blocking=True) if images.is_cuda else rows]
+
+    def _decoded_images(self, batch: dict):
+        """The batch's ``"images"`` as the ``RaggedBatch`` the resize launch takes, decoded on the device where the
+        trainer has the decoder for what the loader handed over."""
+        dev = self.device
         from .resize import RaggedBatch
         images = batch.get("images")
         if self._decoder is not None:
@@ -307,11 +365,7 @@ class Trainer:
         if not isinstance(images, RaggedBatch):
             raise TypeError("resize_crop works on decoded images (the loader decodes, nothing else): the batch needs "
                             f"'images', a RaggedBatch (collate_fn=collate_ragged); got {sorted(batch)}")
-        if not want_clean:
-            views = self._resizer(images.to(dev, non_blocking=True), batch.get("crop_params"), views=("augmented",))
-            return None, views["augmented"]
-        views = self._resizer(images.to(dev, non_blocking=True), batch.get("crop_params"))
-        return views["clean"], views["augmented"]
+        return images
 
     def _batch_index(self, batch: dict) -> torch.Tensor:
         """The batch's ``"index"`` as a host int64 vector (``teacher_cache``)."""
@@ -326,14 +380,19 @@ class Trainer:
         ``mixed_targets`` on the device.  It draws crop, augment and mix, in that order, on the global CPU generator and
         touches neither model, so it may run ahead of the step before it (``prefetch``).  With ``teacher_cache`` also
         ``index`` (on the device), ``index_host`` and ``teacher_cached``, decided here on the host from the rows whose
-        store has been queued; when it is true there is no ``clean``."""
+        store has been queued; when it is true there is no ``clean``.  With ``teacher_partial`` also ``teacher_rows``
+        (see the class): where it names rows, ``clean`` holds those batch positions only."""
         dev = self.device
         index = None
         cached = False
+        rows = None
         if self.teacher_cache is not None:
             index = self._batch_index(batch)
             cached = not isinstance(self.teacher_cache, int) and self.teacher_cache.has(index)
-        clean, student_imgs = self.prepare_views(batch, want_clean=not cached)
+            if self.teacher_partial and not isinstance(self.teacher_cache, int):
+                rows = _teacher_rows(self.teacher_cache.filled(index), self.teacher_partial)
+        partial = rows is not None and rows.numel() > 0
+        clean, student_imgs = self.prepare_views(batch, want_clean=not cached, clean_rows=rows if partial else None)
         targets = batch["label"].to(dev, non_blocking=True)
         mixed_targets = targets
         if (clean is not None and clean.dtype == torch.uint8) or student_imgs.dtype == torch.uint8:
@@ -358,6 +417,8 @@ class Trainer:
             if index.numel() != targets.shape[0]:
                 raise ValueError(f"'index' has {index.numel()} entries for a batch of {targets.shape[0]}")
             prepared.update(index=index.to(dev, non_blocking=True), index_host=index, teacher_cached=cached)
+            if self.teacher_partial:
+                prepared["teacher_rows"] = rows
         return prepared
 
     def step_prepared(self, prepared: dict) -> dict:
@@ -366,6 +427,8 @@ class Trainer:
         student_imgs = prepared["augmented"]
         targets, mixed_targets = prepared["targets"], prepared["mixed_targets"]
         cached = prepared.get("teacher_cached", False)
+        rows = prepared.get("teacher_rows")
+        partial = not cached and rows is not None and rows.numel() > 0
         ac = torch.autocast(dev.type, dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None)
         with ac:
             logits, s_tokens = capture._extract_student(self.model, student_imgs, self.basd_loss.token_layers,
@@ -375,7 +438,12 @@ class Trainer:
                 teacher_tokens, teacher_attns = capture.extract_intermediates(self._teacher, prepared["clean"],
                                                                               attn=self.attn_capture)
         # the loss is computed outside autocast: fp32 logits, tokens consumed in their own dtype (fp32 internal)
-        if cached:
+        if partial:
+            # the teacher saw ``rows`` only: their teacher side as the uncached step at this batch size would make it,
+            # the missing ones of them stored, and the step goes on as the cached one
+            self._store_missing_rows(prepared, self.basd_loss.teacher_side(teacher_tokens, teacher_attns,
+                                                                           as_batch=targets.shape[0]))
+        if cached or partial:
             # the gather is queued HERE, on the step's stream, not where the batch was prepared: it reads rows that
             # stores on this stream wrote
             side = self.teacher_cache.load(prepared["index_host"], device_index=prepared["index"])
@@ -405,6 +473,76 @@ class Trainer:
             from .teacher_cache import TeacherCache
             self.teacher_cache = TeacherCache(self.teacher_cache, side.g.shape[-1], side.omega.shape[-1], self.device)
         self.teacher_cache.store(prepared["index_host"], side, device_index=prepared["index"])
+
+    def _store_missing_rows(self, prepared: dict, side) -> None:
+        """Of the rows ``side`` holds (batch positions ``teacher_rows``) those whose cache row is still not filled NOW:
+        the padding is dropped, and so is a row that a step between this batch's preparation and now has stored
+        (``prefetch``), so a stored row never changes after its first store."""
+        index = prepared["index_host"][prepared["teacher_rows"]]
+        need = ~self.teacher_cache.filled(index)
+        count = int(need.sum())
+        if count == 0:
+            return
+        if bool(need[:count].all()):            # the missing rows come first (``_teacher_rows``): views, no launch
+            side = tuple(t[:count] for t in side)
+        else:
+            keep = torch.nonzero(need).reshape(-1).to(self.device, non_blocking=True)
+            side = tuple(t.index_select(0, keep) for t in side)
+        self.teacher_cache.store(index[need], side)
+
+    def fill_teacher_cache(self, loader, *, as_batch: int) -> int:
+        """Run the frozen teacher over ``loader`` once, without the student, and store every image's teacher side in
+        ``teacher_cache``; returns the number of images stored.  Afterwards every step whose images the loader showed is
+        a cached one, from the first epoch on and on every rank that filled: call it once per rank over the whole dataset
+        before ``train``.
+
+        The loader's batches carry ``"index"`` (``KeyError`` without) and the source of the clean view: ``"clean"``, or
+        ``"images"`` with ``resize_crop`` / ``jpeg_decode`` / ``png_decode``; labels and ``"augmented"`` are not touched.
+        Per batch: the clean view alone (``views=("clean",)`` of the resize launch), the teacher under the step's
+        autocast, ``BASDLoss.teacher_side(..., as_batch=as_batch)``, ``TeacherCache.store``.  No generator is drawn from;
+        no student forward, no selector, no optimizer.  ``as_batch``: the batch size of the TRAINING steps (it fixes the
+        fold order of the split teacher Gram); the loader's own batch size may differ, and the last batch may be short.
+        An int ``teacher_cache`` is built from the first batch's shapes, as in the step.  ``ValueError`` for a
+        token-format teacher or without ``teacher_cache``; on a CPU device the package's "no CPU fallback"
+        ``RuntimeError``.  It runs serially on the current stream and uses the trainer's stage objects: it must not be
+        called while an epoch or a validation runs.  The caveat of ``teacher_partial`` (see the class) holds: a vendor
+        convolution may choose by batch size, so fill at the training batch size where the last bits matter."""
+        if self._teacher.feature_format == "token":
+            raise ValueError("fill_teacher_cache needs a teacher with ONE extracted layer (feature_format != 'token'): "
+                             f"{_TOKEN_FORMAT_WHY}; got feature_format={self._teacher.feature_format!r}")
+        if self.teacher_cache is None:
+            raise ValueError("fill_teacher_cache fills the trainer's teacher_cache; got teacher_cache=None")
+        if isinstance(as_batch, bool) or not isinstance(as_batch, int) or as_batch <= 0:
+            raise ValueError(f"as_batch must be an int > 0, the batch size of the training steps (got {as_batch!r})")
+        from ._launch import require_gpu
+        dev = self.device
+        ac = torch.autocast(dev.type, dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None)
+        stored = 0
+        for batch in loader:
+            index = self._batch_index(batch)
+            require_gpu(dev, "the teacher cache's rows")
+            if self._resizer is None:
+                clean = batch["clean"].to(dev, non_blocking=True)
+            else:
+                images = self._decoded_images(batch).to(dev, non_blocking=True)
+                clean = self._resizer(images, None, views=("clean",))["clean"]
+            if index.numel() != clean.shape[0]:
+                raise ValueError(f"'index' has {index.numel()} entries for a batch of {clean.shape[0]}")
+            if clean.dtype == torch.uint8:
+                self._require_fused("uint8 batches need", "the conversion and the normalisation are part of the fused "
+                                    "launch", TypeError, clean=clean)
+                from .augment import MixParams
+                clean, _ = self._clean_mixer(clean, None, MixParams("none"))
+            with ac, torch.no_grad():
+                teacher_tokens, teacher_attns = capture.extract_intermediates(self._teacher, clean,
+                                                                              attn=self.attn_capture)
+            side = self.basd_loss.teacher_side(teacher_tokens, teacher_attns, as_batch=as_batch)
+            if isinstance(self.teacher_cache, int):
+                from .teacher_cache import TeacherCache
+                self.teacher_cache = TeacherCache(self.teacher_cache, side.g.shape[-1], side.omega.shape[-1], dev)
+            self.teacher_cache.store(index, side)
+            stored += index.numel()
+        return stored
 
     def train_step(self, batch: dict) -> dict:
         return self.step_prepared(self.prepare_batch(batch))

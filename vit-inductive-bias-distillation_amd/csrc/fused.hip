@@ -104,6 +104,56 @@ static int plan_query(const BasdProcrustesArgs* a, long* out20, bool teacher_giv
 int basd_procrustes_plan_query(const BasdProcrustesArgs* a, long* out20) { return plan_query(a, out20, false); }
 // The same for basd_procrustes_forward_cached: field 0 is 5 ("given"), fields 4, 13 and 14 are 0.
 int basd_procrustes_plan_query_cached(const BasdProcrustesArgs* a, long* out20) { return plan_query(a, out20, true); }
+// The same for basd_procrustes_teacher_side: fields 0, 4, 13, 14 and 16 as in basd_procrustes_plan_query, the rest 0.
+int basd_procrustes_plan_query_teacher_side(const BasdProcrustesArgs* a, long* out20) {
+    using namespace basd::plan;
+    BASD_CHECK_ARG(out20);
+    ProcrustesPlan p;
+    BASD_TRY(teacher_side_plan(a, &p));
+    for (int i = 0; i < kPlanFields; ++i) out20[i] = 0;
+    out20[0] = p.center, out20[4] = p.gram_split, out20[13] = p.w_borrow_floats, out20[14] = p.lds_center;
+    out20[16] = p.lds_gram;
+    return p.teacher_status();
+}
+
+// The teacher half of the call, one statement of it for basd_procrustes_forward_fused and
+// basd_procrustes_teacher_side, in the two pieces the uncached call queues around its student projection.
+// Token weights + mixed, centred teacher, once per group (G = 1: shared by all layers), by the centring route of the plan.
+static int teacher_weights_and_centring(const BasdProcrustesArgs* a, const basd::plan::ProcrustesPlan& p, hipStream_t st) {
+    using namespace basd::plan;
+    const int L = (int)a->L, G = (int)a->G, B = (int)a->B, n_s = (int)a->n_s, d_t = (int)a->d_t, n = (int)a->n;
+    const int td = (int)a->t_dtype;
+    for (int g = 0; g < G; ++g) {
+        BASD_TRY(basd_token_weights(a->attn_ptrs, (int)a->a_dtype, a->mix + (long)g * L, L, a->a_sb, a->a_sh, a->a_sq,
+                                    a->a_sk, B, (int)a->H, (int)a->A, (int)a->has_cls, (int)a->n_a, n, n_s, a->atap0,
+                                    a->atap1, a->alam, a->tap0, a->tap1, a->lam, a->omega + (long)g * B * n_s,
+                                    a->omega_t + (long)g * B * n, a->raw ? a->raw + (long)g * B * a->n_a : nullptr, st));
+    }
+    switch (p.center) {
+        case kCenterStreamV4:
+        case kCenterStream:     // its per-chunk column sums borrow W, which is not written before the stacked product
+            return basd_teacher_center_stream(a->tok_ptrs, td, a->mix, L, G, a->t_sb, a->t_sn, a->t_sd, B, n, d_t, a->g0,
+                                              a->g1, a->glam, a->omega_t, a->mu_t, a->tc, a->W, st);
+        case kCenterMulti:
+            return basd_teacher_center_multi(a->tok_ptrs, td, a->mix, L, G, a->t_sb, a->t_sn, a->t_sd, B, n, d_t, a->g0,
+                                             a->g1, a->glam, a->omega_t, a->mu_t, a->tc, st);
+        case kCenterPerGroup:
+            for (int g = 0; g < G; ++g)
+                BASD_TRY(basd_teacher_center(a->tok_ptrs, td, a->mix + (long)g * L, L, a->t_sb, a->t_sn, a->t_sd, B, n, d_t,
+                                             a->g0, a->g1, a->glam, a->omega_t + (long)g * B * n,
+                                             a->mu_t + (long)g * B * d_t, a->tc + (long)g * B * n * d_t, st));
+            return BASD_OK;
+        default:
+            return BASD_EUNSUPPORTED;
+    }
+}
+// The fp64 Gram of the centred teacher into g_b (G*B, n, n), split over the contraction where the plan says so.
+static int teacher_gram(const BasdProcrustesArgs* a, const basd::plan::ProcrustesPlan& p, double* g_b, hipStream_t st) {
+    const int n = (int)a->n, d_t = (int)a->d_t, GB = (int)a->G * (int)a->B;
+    if (p.gram_split)
+        return basd_gram_f64_split(a->tc, (long)n * d_t, n, d_t, GB, (int)a->g_splits, a->g_slabs, g_b, st);
+    return basd_gram_f64(a->tc, (long)n * d_t, n, d_t, GB, g_b, (long)n * n, st);
+}
 
 // relational.py:22-50 for all extraction layers against the (mixed) teacher, forward and -- optionally -- the student
 // gradients for given upstream gradients; see BasdProcrustesArgs in include/basd_hip.h.  The routes are those of the
@@ -120,37 +170,11 @@ static int procrustes_call(const BasdProcrustesArgs* a, hipStream_t st, bool tea
     else BASD_CHECK_ARG(a->tok_ptrs && a->attn_ptrs && a->mix);
     ProcrustesPlan p;
     BASD_TRY(procrustes_plan(a, g_transposed_cores, g_finish_fused, &p, teacher_given));
-    const int E = (int)a->E, L = (int)a->L, G = (int)a->G, B = (int)a->B, n_s = (int)a->n_s;
-    const int d_s = (int)a->d_s, d_t = (int)a->d_t, H = (int)a->H, A = (int)a->A, n_a = (int)a->n_a, n = (int)a->n;
-    const int td = (int)a->t_dtype, sd = (int)a->s_dtype;
-    // teacher side: token weights + mixed, centred teacher, once per group (G = 1: shared by all layers)
-    for (int g = 0; g < G && !teacher_given; ++g) {
-        BASD_TRY(basd_token_weights(a->attn_ptrs, (int)a->a_dtype, a->mix + (long)g * L, L, a->a_sb, a->a_sh, a->a_sq,
-                                    a->a_sk, B, H, A, (int)a->has_cls, n_a, n, n_s, a->atap0, a->atap1, a->alam,
-                                    a->tap0, a->tap1, a->lam, a->omega + (long)g * B * n_s,
-                                    a->omega_t + (long)g * B * n, a->raw ? a->raw + (long)g * B * n_a : nullptr, st));
-    }
-    switch (p.center) {
-        case kCenterStreamV4:
-        case kCenterStream:     // its per-chunk column sums borrow W, which is not written before the stacked product
-            BASD_TRY(basd_teacher_center_stream(a->tok_ptrs, td, a->mix, L, G, a->t_sb, a->t_sn, a->t_sd, B, n, d_t, a->g0,
-                                                a->g1, a->glam, a->omega_t, a->mu_t, a->tc, a->W, st));
-            break;
-        case kCenterMulti:
-            BASD_TRY(basd_teacher_center_multi(a->tok_ptrs, td, a->mix, L, G, a->t_sb, a->t_sn, a->t_sd, B, n, d_t, a->g0,
-                                               a->g1, a->glam, a->omega_t, a->mu_t, a->tc, st));
-            break;
-        case kCenterPerGroup:
-            for (int g = 0; g < G; ++g)
-                BASD_TRY(basd_teacher_center(a->tok_ptrs, td, a->mix + (long)g * L, L, a->t_sb, a->t_sn, a->t_sd, B, n, d_t,
-                                             a->g0, a->g1, a->glam, a->omega_t + (long)g * B * n,
-                                             a->mu_t + (long)g * B * d_t, a->tc + (long)g * B * n * d_t, st));
-            break;
-        case kCenterGiven:
-            break;
-        default:
-            return BASD_EUNSUPPORTED;
-    }
+    const int E = (int)a->E, G = (int)a->G, B = (int)a->B, n_s = (int)a->n_s;
+    const int d_s = (int)a->d_s, n = (int)a->n;
+    const int sd = (int)a->s_dtype;
+    // teacher side (teacher_given: kCenterGiven, nothing is queued)
+    if (!teacher_given) BASD_TRY(teacher_weights_and_centring(a, p, st));
     // student side
     const long om_stride = G == 1 ? 0 : (long)B * n_s;
     if (p.project == kProjectNone) return p.status();
@@ -171,12 +195,8 @@ static int procrustes_call(const BasdProcrustesArgs* a, hipStream_t st, bool tea
     double* g_b = a->g_all + (long)EB * nn;
     double* l_b = a->l_all + (long)EB * nn;
     BASD_TRY(basd_gram_f64(a->a_prime, (long)n * d_s, n, d_s, EB, a->g_all, nn, st));
-    if (teacher_given) {
-        // g_b is the caller's (basd_teacher_cache_load): factored below with the student Grams, as in the uncached call
-    } else if (p.gram_split)
-        BASD_TRY(basd_gram_f64_split(a->tc, (long)n * d_t, n, d_t, GB, (int)a->g_splits, a->g_slabs, g_b, st));
-    else
-        BASD_TRY(basd_gram_f64(a->tc, (long)n * d_t, n, d_t, GB, g_b, nn, st));
+    // (teacher_given: g_b is the caller's (basd_teacher_cache_load), factored below with the student Grams all the same)
+    if (!teacher_given) BASD_TRY(teacher_gram(a, p, g_b, st));
     BASD_TRY(basd_chol_f64(a->g_all, nn, n, EB + GB, a->l_all, nn, st));
     if (p.cores == kCoresTransposed) {
         BASD_TRY(basd_stack_product_t(a->l_all, l_b, nn, n, EB, GB, a->W, 2 * nn, st));
@@ -238,6 +258,17 @@ static int procrustes_call(const BasdProcrustesArgs* a, hipStream_t st, bool tea
 }
 int basd_procrustes_forward_fused(const BasdProcrustesArgs* a, hipStream_t st) { return procrustes_call(a, st, false); }
 int basd_procrustes_forward_cached(const BasdProcrustesArgs* a, hipStream_t st) { return procrustes_call(a, st, true); }
+// The teacher half alone, for ONE teacher layer: see include/basd_hip.h.  Nothing of the student is read or queued.
+int basd_procrustes_teacher_side(const BasdProcrustesArgs* a, hipStream_t st) {
+    using namespace basd::plan;
+    BASD_CHECK_ARG(a && a->tok_ptrs && a->attn_ptrs && a->mix && a->omega && a->omega_t && a->mu_t && a->tc && a->g_all);
+    ProcrustesPlan p;
+    BASD_TRY(teacher_side_plan(a, &p));
+    if (p.teacher_status() != BASD_OK) return p.teacher_status();       // before anything is queued
+    BASD_CHECK_ARG(!p.gram_split || a->g_splits <= 64);
+    BASD_TRY(teacher_weights_and_centring(a, p, st));
+    return teacher_gram(a, p, a->g_all, st);
+}
 
 // Events for ordering two streams from inside a library call (see basd_tridiag_ranked's mid_event).
 int basd_event_create(void** out) {

@@ -108,8 +108,45 @@ struct ProcrustesPlan {
         const bool routed = center != kCenterNone && lds_gram >= 0 && chol != kCholNone && finish != kFinishNone;
         return routed ? BASD_OK : BASD_EUNSUPPORTED;
     }
+    // the same for basd_procrustes_teacher_side, which ends behind the teacher Gram: asked BEFORE anything is queued
+    int teacher_status() const { return center != kCenterNone && lds_gram >= 0 ? BASD_OK : BASD_EUNSUPPORTED; }
 };
 constexpr int kPlanFields = 20;
+
+// The teacher half of a plan, the one statement of it for the uncached call and for basd_procrustes_teacher_side: the
+// centring route with what it borrows, whether the teacher Gram is split, the Gram's LDS (-1: past LDS).
+inline void plan_teacher_half(const BasdProcrustesArgs* a, ProcrustesPlan* p) {
+    const int E = (int)a->E, L = (int)a->L, G = (int)a->G, B = (int)a->B, d_t = (int)a->d_t, n = (int)a->n;
+    // all groups in one pass over the teacher layers where that applies
+    const long borrow = stream_scratch_floats(G, B, n, d_t);
+    if (G > 1 && L >= 4 && borrow <= core_floats(E, B, n) && stream_applies(G, a->t_sd, B)) {
+        p->center = stream_v4_applies((int)a->t_dtype, a->g0 != nullptr, a->t_sb, a->t_sn, d_t, a->tc, a->W)
+                        ? kCenterStreamV4 : kCenterStream;
+        p->w_borrow_floats = borrow;
+    } else if (G > 1 && center_multi_applies(G, n)) {
+        p->center = kCenterMulti;
+        p->lds_center = (long)center_multi_lds(G, n);
+    } else if (center_fits(n)) {
+        p->center = kCenterPerGroup;
+        p->lds_center = (long)center_lds(n);
+    }
+    p->gram_split = a->g_slabs && a->g_splits > 1;
+    p->lds_gram = gram_fits(n) ? (long)gram_lds(n) : -1;
+}
+
+// The plan of basd_procrustes_teacher_side: the teacher half for ONE layer and ONE group, every student-side stage
+// "none" (0).  The student's fields of the block (E, d_s, the student pointers and layout) are not read.  More than one
+// layer or group: no route (teacher_status() is BASD_EUNSUPPORTED), as for a core grid past the centring kernel's LDS.
+inline int teacher_side_plan(const BasdProcrustesArgs* a, ProcrustesPlan* out) {
+    BASD_CHECK_ARG(a && out);
+    const int L = (int)a->L, G = (int)a->G, B = (int)a->B, n_s = (int)a->n_s, n_t = (int)a->n_t, n = (int)a->n;
+    BASD_CHECK_ARG(L > 0 && G > 0 && B > 0 && n > 0 && n == (n_s < n_t ? n_s : n_t) && a->d_t > 0);
+    BASD_CHECK_ARG(B <= 65535);               // samples index grid.y of the centring kernel
+    ProcrustesPlan p = {};
+    if (L == 1 && G == 1) plan_teacher_half(a, &p);
+    *out = p;
+    return BASD_OK;
+}
 
 // Shapes and presence of the optional pointers are read from the call's own argument block; transposed_hook and
 // finish_hook are the settings of basd_procrustes_tuning / basd_procrustes_finish_tuning.  teacher_given: the plan of
@@ -125,20 +162,12 @@ inline int procrustes_plan(const BasdProcrustesArgs* a, int transposed_hook, int
     const int EB = E * B;
     ProcrustesPlan p = {};
 
-    // teacher side: all groups in one pass over the teacher layers where that applies
-    const long borrow = stream_scratch_floats(G, B, n, d_t);
+    // teacher side (the student Grams share the Gram kernel, hence its LDS either way)
     if (teacher_given) {
         p.center = kCenterGiven;
-    } else if (G > 1 && L >= 4 && borrow <= core_floats(E, B, n) && stream_applies(G, a->t_sd, B)) {
-        p.center = stream_v4_applies((int)a->t_dtype, a->g0 != nullptr, a->t_sb, a->t_sn, d_t, a->tc, a->W)
-                       ? kCenterStreamV4 : kCenterStream;
-        p.w_borrow_floats = borrow;
-    } else if (G > 1 && center_multi_applies(G, n)) {
-        p.center = kCenterMulti;
-        p.lds_center = (long)center_multi_lds(G, n);
-    } else if (center_fits(n)) {
-        p.center = kCenterPerGroup;
-        p.lds_center = (long)center_lds(n);
+        p.lds_gram = gram_fits(n) ? (long)gram_lds(n) : -1;
+    } else {
+        plan_teacher_half(a, &p);
     }
 
     // student side: all layers in one launch where the vectorised kernel applies
@@ -153,8 +182,6 @@ inline int procrustes_plan(const BasdProcrustesArgs* a, int transposed_hook, int
         p.lds_project = (long)(multi ? project_multi_lds(n_s) : project_lds(n_s));
     }
 
-    p.gram_split = !teacher_given && a->g_slabs && a->g_splits > 1;
-    p.lds_gram = gram_fits(n) ? (long)gram_lds(n) : -1;
     p.chol = chol_in_lds(n) ? kCholLds : chol_blocked_fits(n) ? kCholBlocked : kCholNone;
     p.lds_chol = (long)(p.chol == kCholLds ? chol_lds(n) : chol_blocked_lds(n));
 
