@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(256) teacher_factor_kernel(
                 const float l1 = lam[s];
                 const float ca = (tap0[s] == a ? 1.f - l1 : 0.f) + (tap1[s] == a ? l1 : 0.f);
                 const float cb = (tap0[s] == bb ? 1.f - l1 : 0.f) + (tap1[s] == bb ? l1 : 0.f);
-                q = fmaf(w[s] * ca, cb, q);
+                q = fmaf(w[s], ca * cb, q);      // ca * cb commutes: Q, and with it Kt, is symmetric bit for bit
             }
         } else if (a == bb) {
             q = w[a];
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(256) teacher_kt_tiled_kernel(
                 const float l1 = lam[s];
                 const float ca = (tap0[s] == a ? 1.f - l1 : 0.f) + (tap1[s] == a ? l1 : 0.f);
                 const float cb = (tap0[s] == bb ? 1.f - l1 : 0.f) + (tap1[s] == bb ? l1 : 0.f);
-                q = fmaf(w[s] * ca, cb, q);
+                q = fmaf(w[s], ca * cb, q);      // ca * cb commutes: Q, and with it Kt, is symmetric bit for bit
             }
         } else if (a == bb) {
             q = w[a];
