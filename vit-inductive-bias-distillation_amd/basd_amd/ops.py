@@ -6,6 +6,7 @@ arithmetic on the path runs in ``libbasd_hip.so``.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass
 from functools import lru_cache
 from typing import NamedTuple
@@ -732,14 +733,48 @@ def _plan_taps(n_s: int, n_t: int, n_a: int, dev: torch.device) -> tuple:
             taps(n_a, n_s, dev))
 
 
+def _tap_ptrs(tp: Taps | None, ranges: bool = False) -> tuple:
+    """Device pointers (tap0, tap1, lam) of ``tp``, with ``ranges`` also (range0, range1); all ``None`` for the identity."""
+    if tp is None:
+        return (None,) * (5 if ranges else 3)
+    ptrs = (tp.tap0.data_ptr(), tp.tap1.data_ptr(), tp.lam.data_ptr())
+    return ptrs + (tp.range0.data_ptr(), tp.range1.data_ptr()) if ranges else ptrs
+
+
 def _set_taps(a, tp: Taps | None, gt: Taps | None, atp: Taps | None) -> None:
-    if atp:
-        a.atap0, a.atap1, a.alam = atp.tap0.data_ptr(), atp.tap1.data_ptr(), atp.lam.data_ptr()
-    if tp:
-        a.tap0, a.tap1, a.lam = tp.tap0.data_ptr(), tp.tap1.data_ptr(), tp.lam.data_ptr()
-        a.range0, a.range1 = tp.range0.data_ptr(), tp.range1.data_ptr()
-    if gt:
-        a.g0, a.g1, a.glam = gt.tap0.data_ptr(), gt.tap1.data_ptr(), gt.lam.data_ptr()
+    a.atap0, a.atap1, a.alam = _tap_ptrs(atp)
+    a.tap0, a.tap1, a.lam, a.range0, a.range1 = _tap_ptrs(tp, ranges=True)
+    a.g0, a.g1, a.glam = _tap_ptrs(gt)
+
+
+def _set_teacher_args(a, teachers: list[torch.Tensor], attns: list[torch.Tensor], tabs: tuple | None) -> None:
+    """The teacher half of a ``ProcrustesArgs`` for L token and L attention tensors of one layout each.  The pointer
+    tables and the attention layout are a call's; the token layout and the taps (``tabs``, of ``_plan_taps``) are in the
+    key of a cached plan, which has set them already: such a call passes ``tabs=None``."""
+    t0, a0 = teachers[0], attns[0]
+    a.tok_ptrs, a.attn_ptrs = _ptr_table(teachers).data_ptr(), _ptr_table(attns).data_ptr()
+    a.a_dtype = _dtype_code(a0)
+    a.a_sb, a.a_sh, a.a_sq, a.a_sk = a0.stride()
+    if tabs is not None:
+        a.t_dtype, a.t_sb, a.t_sn, a.t_sd = _dtype_code(t0), *t0.stride()
+        _set_taps(a, *tabs)
+
+
+def _student_intake(students: list[torch.Tensor]) -> tuple[list[torch.Tensor], tuple]:
+    """The student token tensors as the kernels read them (fp32 or bf16, unit feature stride, one shape and layout) and
+    ``s_layout``, what the routes depend on besides the shapes: (dtype code, batch stride, token stride, whether every
+    layer starts on a 16-byte boundary)."""
+    xs = [as_supported(x) for x in students]
+    xs = _check_common_layout([x if x.stride(2) == 1 else x.contiguous() for x in xs], "student token tensors")
+    x0 = xs[0]
+    return xs, (_dtype_code(x0), x0.stride(0), x0.stride(1), int(all(x.data_ptr() % 16 == 0 for x in xs)))
+
+
+# What a ``_ProcrustesPlan`` is built from and, for ``procrustes_forward``, the key it is cached under.  two_pass_svd:
+# TWO_PASS_SVD when the call was made; s_layout: of ``_student_intake``; t_layout: (dtype code, batch stride, token
+# stride, feature stride) of the teacher tokens
+_ProcrustesCall = namedtuple("_ProcrustesCall", "E L B n_s d_s n_t d_t H A has_cls need_bwd need_mix_grad want_sweeps "
+                             "want_dx want_uw dev stream two_pass_svd s_layout t_layout")
 
 
 class _ProcrustesPlan:
@@ -747,7 +782,8 @@ class _ProcrustesPlan:
 
     Scratch (mixed teacher, fp64 Grams / factors, stacked cores, Jacobi flags, ...) is only alive inside the call's own
     launches on ONE stream, so it is allocated once and reused by every step; what outlives the call -- the tensors kept
-    for the backward and the student gradients handed to autograd -- is allocated per call (two ``torch.empty``)."""
+    for the backward and the student gradients handed to autograd -- is allocated per call (two ``torch.empty``, in
+    ``begin``).  A call is: plan, ``begin``, the caller's own teacher part, the launch, ``finish``."""
 
     # names of the routes basd_procrustes_plan_query answers with (include/basd_hip.h), in its order
     ROUTE_FIELDS = ("center", "project", "slab_width", "slabs", "gram_split", "chol", "cores", "svd", "finish",
@@ -759,66 +795,67 @@ class _ProcrustesPlan:
         """The C planner's routes for ``self.args`` under the hooks as they stand (no HIP call)."""
         import ctypes
         out = (ctypes.c_long * len(self.ROUTE_FIELDS))()
-        name = "basd_procrustes_plan_query_cached" if self.given else "basd_procrustes_plan_query"
+        name = "basd_procrustes_plan_query_cached" if self.teacher_given else "basd_procrustes_plan_query"
         status = _lib.query(name, ctypes.addressof(self.args), ctypes.cast(out, ctypes.c_void_p))
         if status != 0:
             raise RuntimeError(f"{name} failed with status {status} (invalid argument / unsupported shape)")
         return dict(zip(self.ROUTE_FIELDS, out))
 
-    def __init__(self, E, L, B, n_s, d_s, n_t, d_t, H, A, has_cls, need_bwd, need_mix_grad, want_sweeps, want_dx,
-                 want_uw, s_layout, t_layout, dev, given=False):
+    def __init__(self, c: _ProcrustesCall, teacher_given: bool = False):
         import ctypes
-        # given: the plan of ``procrustes_forward_cached`` -- the teacher side is an input, so the teacher-side scratch
-        # (tc, mu_t, the split Gram's slabs) is not allocated and the cached planner is the one asked
-        self.given = given
-        self.E, self.L, self.B, self.n_s, self.d_s, self.n_t, self.d_t = E, L, B, n_s, d_s, n_t, d_t
-        n_a = A - (1 if has_cls else 0)
-        n = min(n_s, n_t)
-        self.n, self.n_a = n, n_a
+        # teacher_given: the plan of ``procrustes_forward_cached`` (see ``given``) -- the cached planner is the one asked
+        self.teacher_given = teacher_given
+        E, L, B, n_s, d_s, n_t, d_t, dev = c.E, c.L, c.B, c.n_s, c.d_s, c.n_t, c.d_t, c.dev
+        self.E, self.L, self.B, self.n_s, self.d_s, self.dev = E, L, B, n_s, d_s, dev
+        self.need_bwd, self.need_mix_grad, self.want_dx = c.need_bwd, c.need_mix_grad, c.want_dx
+        n_a = self.n_a = c.A - (1 if c.has_cls else 0)
+        n = self.n = min(n_s, n_t)
         self.tp, self.gt, self.atp = _plan_taps(n_s, n_t, n_a, dev)
         G = self.G = 1 if L == 1 else E          # softmax over one layer is exactly 1: the teacher side is shared
         f32 = dict(device=dev, dtype=torch.float32)
         EB, GB = E * B, G * B
-        self.need_bwd, self.need_mix_grad, self.want_dx, self.want_uw = need_bwd, need_mix_grad, want_dx, want_uw
         # ---- kept sizes (fresh per call): omega, mu_s, a_prime, k_prime, terms (4, E, B), uw
-        self.kept_sizes = [G * B * n_s, E * B * d_s, EB * n * d_s, EB * n * n if need_bwd else 0, 4 * EB,
-                           (4 + 2 * E) if want_uw else 0]
+        self.kept_sizes = [G * B * n_s, E * B * d_s, EB * n * d_s, EB * n * n if c.need_bwd else 0, 4 * EB,
+                           (4 + 2 * E) if c.want_uw else 0]
         # every piece starts on a 256-byte boundary, as separate allocations would (the kernels read them as float4)
-        self.kept_padded = [(c + 63) // 64 * 64 for c in self.kept_sizes]
+        self.kept_padded = [(s + 63) // 64 * 64 for s in self.kept_sizes]
         self.kept_total = sum(self.kept_padded)
-        # ---- scratch
-        g_splits = self.g_splits = 1 if given else teacher_gram_splits(GB, d_t)
+        # ---- scratch.  A given teacher side needs none for the teacher's features: a feature width of 0 leaves tc and
+        # mu_t empty and the Gram unsplit (no slabs)
+        t_width = 0 if teacher_given else d_t
+        g_splits = teacher_gram_splits(GB, t_width)
         self.g_all = torch.empty((EB + GB + (g_splits * GB if g_splits > 1 else 0), n, n), device=dev, dtype=torch.float64)
         self.l_all = torch.empty((EB + GB, n, n), device=dev, dtype=torch.float64)
         self.W = torch.empty((EB, n, 2 * n), **f32)        # memory == column-major (2n x n)
-        self.tc = torch.empty((0,) if given else (G, B, n, d_t), **f32)
+        self.tc = torch.empty((G, B, n, t_width), **f32)
         self.ints = torch.empty((_lib.query("basd_jacobi_workspace_ints", EB, MAX_SWEEPS) + EB,), device=dev,
                                 dtype=torch.int32)
-        self.sweeps = self.ints[-EB:] if want_sweeps else None
-        self.h = torch.empty((E, B, n, d_s), **f32) if want_dx else None
+        self.sweeps = self.ints[-EB:] if c.want_sweeps else None
+        self.h = torch.empty((E, B, n, d_s), **f32) if c.want_dx else None
         self.host_ptrs = (ctypes.c_void_p * E)()
+        self.grad_layers = None       # a call's cast ``grad_layers``, alive until the next call (see ``begin``)
 
         a = self.args = _lib.ProcrustesArgs()
         a.student_host_ptrs = ctypes.cast(self.host_ptrs, ctypes.c_void_p)
         (a.E, a.L, a.G, a.B, a.n_s, a.n_t, a.d_s, a.d_t, a.H, a.A, a.has_cls, a.n_a, a.n, a.max_sweeps) = \
-            E, L, G, B, n_s, n_t, d_s, d_t, H, A, int(has_cls), n_a, n, MAX_SWEEPS
-        a.s_dtype, a.s_sb, a.s_sn, a.s_aligned = s_layout
-        a.t_dtype, a.t_sb, a.t_sn, a.t_sd = t_layout
-        a.g_splits = g_splits
-        a.g_slabs = self.g_all[EB + GB:].data_ptr() if g_splits > 1 else None
-        a.tc, a.W = self.tc.data_ptr(), self.W.data_ptr()
+            E, L, G, B, n_s, n_t, d_s, d_t, c.H, c.A, int(c.has_cls), n_a, n, MAX_SWEEPS
+        a.s_dtype, a.s_sb, a.s_sn, a.s_aligned = c.s_layout
+        a.t_dtype, a.t_sb, a.t_sn, a.t_sd = c.t_layout
+        a.g_splits, a.g_slabs = g_splits, self.g_all[EB + GB:].data_ptr() if g_splits > 1 else None
+        a.g_all, a.l_all, a.W, a.tc = self.g_all.data_ptr(), self.l_all.data_ptr(), self.W.data_ptr(), self.tc.data_ptr()
+        a.jflags, a.sweeps, a.h = self.ints.data_ptr(), _ptr(self.sweeps), _ptr(self.h)
         # Which routes the call will take is the C planner's decision.  It is asked with what this call offers: the
         # per-call tensors (allocated 256-byte aligned) and the optional workspaces stand in as OFFERED; the two-pass
         # log is not offered to very large batches or with little free memory (the block solver needs no log), U Sigma
         # rebuilt from the transposed cores not when TRANSPOSED_MIX_GRAD is off.
         OFFERED = 256
         a.mu_s = a.a_prime = OFFERED
-        a.k_prime = OFFERED if need_bwd else None
-        a.dx = OFFERED if want_dx else None
-        a.raw = OFFERED if need_mix_grad else None
-        a.uw_ce = OFFERED if want_uw else None
-        a.w_stack = OFFERED if need_mix_grad and need_bwd and TRANSPOSED_MIX_GRAD else None
-        jac_bytes = _lib.query("basd_jacobi_twopass_workspace_bytes", n, EB, MAX_SWEEPS) if TWO_PASS_SVD else 0
+        a.k_prime = OFFERED if c.need_bwd else None
+        a.dx = OFFERED if c.want_dx else None
+        a.raw = OFFERED if c.need_mix_grad else None
+        a.uw_ce = OFFERED if c.want_uw else None
+        a.w_stack = OFFERED if c.need_mix_grad and c.need_bwd and TRANSPOSED_MIX_GRAD else None
+        jac_bytes = _lib.query("basd_jacobi_twopass_workspace_bytes", n, EB, MAX_SWEEPS) if c.two_pass_svd else 0
         if jac_bytes > TWO_PASS_LOG_LIMIT or (jac_bytes > (256 << 20)
                                               and jac_bytes > torch.cuda.mem_get_info(dev)[0] // 2):
             jac_bytes = 0
@@ -829,28 +866,91 @@ class _ProcrustesPlan:
         # take.  The others are cached and outlive a change of the (process-wide) hooks: of ``route`` they use only what
         # no hook changes -- tr_part_floats, w_borrow_floats -- and keep the log whenever it is offered, so that the
         # stacked cores find it under any setting.
-        keep_log = jac_bytes > 0 and (route["svd"] == self.TWO_PASS or not need_mix_grad)
+        keep_log = jac_bytes > 0 and (route["svd"] == self.TWO_PASS or not c.need_mix_grad)
         self.jac_ws = torch.empty((jac_bytes // 8 + 1,), device=dev, dtype=torch.int64) if keep_log else None
         # gradients through the mixing weights read U Sigma (the top half of the stacked cores): where the forward takes
         # the transposed route (cores the plain LDS solver holds), it is rebuilt into this buffer
         self.w_stack = torch.empty((EB, n, 2 * n), **f32) if route["rebuild_usigma"] else None
         self.sigma_u = torch.empty((EB, n), **f32) if route["rebuild_usigma"] else None
-        sizes = [GB * n, 0 if given else GB * d_t, route["tr_part_floats"], EB * n]
-        padded = [(c + 63) // 64 * 64 for c in sizes]
+        sizes = [GB * n, GB * t_width, route["tr_part_floats"], EB * n]
+        padded = [(s + 63) // 64 * 64 for s in sizes]
         self.omega_t, self.mu_t, self.tr_part, self.sigma = (
-            piece[:c] for piece, c in zip(torch.split(torch.empty((sum(padded),), **f32), padded), sizes))
+            piece[:s] for piece, s in zip(torch.split(torch.empty((sum(padded),), **f32), padded), sizes))
+        # the offers of the plan's own workspaces give way to what the routes made of them; the per-call ones to ``begin``
+        a.jac_ws, a.w_stack, a.sigma_u = _ptr(self.jac_ws), _ptr(self.w_stack), _ptr(self.sigma_u)
+        a.omega_t, a.mu_t, a.tr_part, a.sigma = (self.omega_t.data_ptr(), self.mu_t.data_ptr(), self.tr_part.data_ptr(),
+                                                 self.sigma.data_ptr())
         _set_taps(a, self.tp, self.gt, self.atp)
-        a.omega_t, a.mu_t, a.tc, a.tr_part = (self.omega_t.data_ptr(), self.mu_t.data_ptr(), self.tc.data_ptr(),
-                                              self.tr_part.data_ptr())
-        a.g_all, a.l_all, a.W = self.g_all.data_ptr(), self.l_all.data_ptr(), self.W.data_ptr()
-        a.sigma, a.jflags, a.sweeps = self.sigma.data_ptr(), self.ints.data_ptr(), _ptr(self.sweeps)
-        a.h = _ptr(self.h)
-        a.jac_ws = _ptr(self.jac_ws)
-        a.w_stack = _ptr(self.w_stack)
-        a.sigma_u = _ptr(self.sigma_u)
+
+    @classmethod
+    def given(cls, E, B, n_s, d_s, n, need_bwd, want_sweeps, want_dx, want_uw, dev, stream, two_pass_svd, s_layout):
+        """The plan of a call whose teacher side is GIVEN on a core grid of ``n`` tokens; the parameters are the cache
+        key of ``procrustes_forward_cached`` behind its tag.  The teacher's own token grid, width and attention do not
+        matter any more, and this is the one place that says what stands for them: the core grid for ``n_t`` (it decides
+        the student-side taps exactly as ``n_t < n_s`` does), ``d_t = H = 1``, ``A = n_s`` without a CLS token (no
+        attention taps), a unit feature stride; one layer, no mixing-weight gradient."""
+        return cls(_ProcrustesCall(E, 1, B, n_s, d_s, n, 1, 1, n_s, False, need_bwd, False, want_sweeps, want_dx, want_uw,
+                                   dev, stream, two_pass_svd, s_layout, t_layout=(0, 0, 0, 1)), teacher_given=True)
+
+    def begin(self, students: list[torch.Tensor], grad_layers: torch.Tensor | None,
+              uwso_ce: torch.Tensor | None) -> ProcrustesContext:
+        """The first half of a call's frame: allocates what outlives the call -- ``kept`` in one piece, ``raw`` for a
+        mixing-weight gradient, ``dx`` --, resets the sweep counts and writes the student side and every output into
+        ``args``.  Returns the call's context, complete but for ``sweeps`` (``finish``); ``teacher_side`` (one teacher
+        layer) are the slots the launch reads or writes, ``mixgrad`` holds ``raw`` alone."""
+        E, B, n_s, d_s, n, G, dev = self.E, self.B, self.n_s, self.d_s, self.n, self.G, self.dev
+        kept = torch.empty((self.kept_total,), device=dev, dtype=torch.float32)
+        omega, mu_s, a_prime, k_prime, terms, uw = (piece[:s] for piece, s in
+                                                    zip(torch.split(kept, self.kept_padded), self.kept_sizes))
+        omega, mu_s = omega.view(G, B, n_s), mu_s.view(E, B, d_s)
+        a_prime = a_prime.view(E, B, n, d_s)
+        k_prime = k_prime.view(E, B, n, n) if self.need_bwd else None
+        terms = terms.view(4, E, B)
+        uw = uw if uwso_ce is not None else None
+        raw = torch.empty((G, B, self.n_a), device=dev, dtype=torch.float32) if self.need_mix_grad else None
+        dx = torch.empty((E, B, n_s, d_s), device=dev, dtype=torch.float32) if self.want_dx else None
+        if self.sweeps is not None:
+            self.sweeps.zero_()
+        if uwso_ce is not None:
+            assert uwso_ce.dtype == torch.float32 and uwso_ce.numel() == 1 and uwso_ce.device == dev
+        if grad_layers is not None:
+            # held by the plan: the launch that reads it is queued after this returns
+            grad_layers = self.grad_layers = grad_layers.contiguous().float()
+
+        args = self.args
+        for e, s in enumerate(students):
+            self.host_ptrs[e] = s.data_ptr()
+        args.student_ptrs = _ptr_table(students).data_ptr()
+        args.omega, args.raw, args.mu_s = omega.data_ptr(), _ptr(raw), mu_s.data_ptr()
+        args.tr_s, args.tr_t, args.nuc, args.loss_b = (terms[i].data_ptr() for i in range(4))
+        args.a_prime, args.k_prime = a_prime.data_ptr(), _ptr(k_prime)
+        args.dx, args.grad_layers = _ptr(dx), _ptr(grad_layers)
+        args.uw_ce, args.uw_out = _ptr(uwso_ce), _ptr(uw)
+        EB = E * B
+        side = TeacherSide(self.g_all[EB:EB + B], omega[0], self.omega_t.view(B, n)) if self.L == 1 else None
+        return ProcrustesContext(omega, mu_s, a_prime, k_prime, terms[0], terms[1], terms[2], terms[3], None,
+                                 dict(raw=raw) if self.need_mix_grad else None, dx, uw, side)
+
+    def finish(self, ctx: ProcrustesContext) -> ProcrustesContext:
+        """The second half, behind the launch: the sweep counts leave the plan's scratch."""
+        ctx.sweeps = self.sweeps.clone() if self.sweeps is not None else None
+        return ctx
 
 
 _PROCRUSTES_PLANS: dict = {}
+
+
+def _cached_plan(key: tuple, build) -> _ProcrustesPlan:
+    """The plan cached under ``key``; ``build()`` makes it where there is none yet.  Eight plans at the most: the ninth
+    clears the cache, behind a device-wide wait, since queued launches may still use the scratch of the plans dropped."""
+    plan = _PROCRUSTES_PLANS.get(key)
+    if plan is None:
+        plan = build()
+        if len(_PROCRUSTES_PLANS) >= 8:
+            torch.cuda.synchronize(plan.dev)
+            _PROCRUSTES_PLANS.clear()
+        _PROCRUSTES_PLANS[key] = plan
+    return plan
 
 
 def procrustes_forward(students: list[torch.Tensor], teachers: list[torch.Tensor], attns: list[torch.Tensor],
@@ -865,90 +965,43 @@ def procrustes_forward(students: list[torch.Tensor], teachers: list[torch.Tensor
     (combined.py:76-85) is computed inside the call as well -- ``ctx.uw`` = [w_ce, w_geo, total, geo, E x w_geo / E,
     E per-layer means] -- and ``ctx.dx`` are then the gradients of ``total`` for a unit upstream gradient.
     Everything is queued by ONE library call (basd_procrustes_forward_fused) into a persistent, shape-keyed workspace
-    (``_ProcrustesPlan``): what the step's host time buys is two allocations and a handful of pointer updates."""
+    (``_ProcrustesPlan``): what the step's host time buys is two allocations and a handful of pointer updates
+    (``_ProcrustesPlan.begin``)."""
     import ctypes
-    E, L = len(students), len(teachers)
-    students = [as_supported(s) for s in students]
-    students = _check_common_layout([s if s.stride(2) == 1 else s.contiguous() for s in students],
-                                    "student token tensors")
+    students, s_layout = _student_intake(students)
     teachers = _check_common_layout([as_supported(t) for t in teachers], "teacher token tensors")
     attns = _check_common_layout([as_supported(a) for a in attns], "teacher attention tensors")
     _require_cuda(*students, *teachers, *attns, mix)
     s0, t0, a0 = students[0], teachers[0], attns[0]
-    dev = s0.device
     B, n_s, d_s = s0.shape
     _, n_t, d_t = t0.shape
-    H, A = a0.shape[1], a0.shape[2]
-    need_bwd = need_backward or grad_layers is not None
-    want_dx = grad_layers is not None or uwso_ce is not None
     stream = _stream()
-    # what the routes depend on besides the shapes: element types, strides, 16-byte alignment of the student layers
-    s_layout = (_dtype_code(s0), s0.stride(0), s0.stride(1), int(all(s.data_ptr() % 16 == 0 for s in students)))
-    t_layout = (_dtype_code(t0), *t0.stride())
+    # the description of the call is its plan's cache key
+    call = _ProcrustesCall(len(students), len(teachers), B, n_s, d_s, n_t, d_t, a0.shape[1], a0.shape[2], bool(has_cls),
+                           need_backward or grad_layers is not None, need_mix_grad, want_sweeps,
+                           grad_layers is not None or uwso_ce is not None, uwso_ce is not None, s0.device, stream,
+                           TWO_PASS_SVD, s_layout, (_dtype_code(t0), *t0.stride()))
     # mixing-weight gradients read the call's scratch in backward (W, sigma, tc, Grams): those calls get private scratch,
     # planned per call (under the hooks of that call)
-    key = (E, L, B, n_s, d_s, n_t, d_t, H, A, bool(has_cls), need_bwd, need_mix_grad, want_sweeps, want_dx,
-           uwso_ce is not None, dev, stream, TWO_PASS_SVD, s_layout, t_layout)
-    plan = None if need_mix_grad else _PROCRUSTES_PLANS.get(key)
-    if plan is None:
-        plan = _ProcrustesPlan(E, L, B, n_s, d_s, n_t, d_t, H, A, has_cls, need_bwd, need_mix_grad, want_sweeps, want_dx,
-                               uwso_ce is not None, s_layout, t_layout, dev)
-        if not need_mix_grad:
-            if len(_PROCRUSTES_PLANS) >= 8:
-                torch.cuda.synchronize(dev)
-                _PROCRUSTES_PLANS.clear()
-            _PROCRUSTES_PLANS[key] = plan
-    n, n_a, G = plan.n, plan.n_a, plan.G
-    EB = E * B
+    plan = _ProcrustesPlan(call) if need_mix_grad else _cached_plan(call, lambda: _ProcrustesPlan(call))
     mix = mix.contiguous().float()
-    kept = torch.empty((plan.kept_total,), device=dev, dtype=torch.float32)
-    omega, mu_s, a_prime, k_prime, terms, uw = (piece[:c] for piece, c in
-                                                zip(torch.split(kept, plan.kept_padded), plan.kept_sizes))
-    omega, mu_s = omega.view(G, B, n_s), mu_s.view(E, B, d_s)
-    a_prime = a_prime.view(E, B, n, d_s)
-    k_prime = k_prime.view(E, B, n, n) if need_bwd else None
-    terms = terms.view(4, E, B)
-    uw = uw if uwso_ce is not None else None
-    raw = torch.empty((G, B, n_a), device=dev, dtype=torch.float32) if need_mix_grad else None
-    dx = torch.empty((E, B, n_s, d_s), device=dev, dtype=torch.float32) if want_dx else None
-    if plan.sweeps is not None:
-        plan.sweeps.zero_()
-    if uwso_ce is not None:
-        assert uwso_ce.dtype == torch.float32 and uwso_ce.numel() == 1 and uwso_ce.device == dev
-    if grad_layers is not None:
-        grad_layers = grad_layers.contiguous().float()
-
+    ctx = plan.begin(students, grad_layers, uwso_ce)
     args = plan.args
-    for e, s in enumerate(students):
-        plan.host_ptrs[e] = s.data_ptr()
-    args.student_ptrs = _ptr_table(students).data_ptr()
-    args.tok_ptrs = _ptr_table(teachers).data_ptr()
-    args.attn_ptrs = _ptr_table(attns).data_ptr()
-    args.a_dtype = _dtype_code(a0)
-    args.a_sb, args.a_sh, args.a_sq, args.a_sk = a0.stride()
+    _set_teacher_args(args, teachers, attns, None)
     args.mix = mix.data_ptr()
-    args.omega, args.raw, args.mu_s = omega.data_ptr(), _ptr(raw), mu_s.data_ptr()
-    args.tr_s, args.tr_t, args.nuc, args.loss_b = (terms[i].data_ptr() for i in range(4))
-    args.a_prime, args.k_prime = a_prime.data_ptr(), _ptr(k_prime)
-    args.dx, args.grad_layers = _ptr(dx), _ptr(grad_layers)
-    args.uw_ce, args.uw_out = _ptr(uwso_ce), _ptr(uw)
     gpu_mark("procrustes_begin")
     _lib.call("basd_procrustes_forward_fused", ctypes.addressof(args), stream)
     gpu_mark("procrustes_end")
 
-    mixgrad = None
     if need_mix_grad:
-        l_a, g_b = plan.l_all[:EB], plan.g_all[EB:EB + G * B]
+        EB = call.E * B
         in_w_stack = plan.route["usigma_in"] == plan.IN_W_STACK
-        mixgrad = dict(raw=raw, tc=plan.tc, l_a=l_a, g_b=g_b, W=plan.w_stack if in_w_stack else plan.W,
-                       sigma=plan.sigma_u if in_w_stack else plan.sigma, omega_e=omega,
-                       teachers=teachers, attns=attns, tok_tab=_ptr_table(teachers), att_tab=_ptr_table(attns),
-                       has_cls=has_cls, n_a=n_a, n=n, n_s=n_s, gather=plan.gt, student_taps=plan.tp, attn_taps=plan.atp,
-                       route=plan.route)
-    sweeps = plan.sweeps.clone() if plan.sweeps is not None else None
-    side = TeacherSide(plan.g_all[EB:EB + B], omega[0], plan.omega_t.view(B, n)) if L == 1 else None
-    return ProcrustesContext(omega, mu_s, a_prime, k_prime, terms[0], terms[1], terms[2], terms[3], sweeps, mixgrad,
-                             dx, uw, side)
+        ctx.mixgrad.update(tc=plan.tc, l_a=plan.l_all[:EB], g_b=plan.g_all[EB:EB + plan.G * B],
+                           W=plan.w_stack if in_w_stack else plan.W, sigma=plan.sigma_u if in_w_stack else plan.sigma,
+                           omega_e=ctx.omega, teachers=teachers, attns=attns, tok_tab=_ptr_table(teachers),
+                           att_tab=_ptr_table(attns), has_cls=has_cls, n_a=plan.n_a, n=plan.n, n_s=n_s, gather=plan.gt,
+                           student_taps=plan.tp, attn_taps=plan.atp, route=plan.route)
+    return plan.finish(ctx)
 
 
 def procrustes_forward_cached(students: list[torch.Tensor], teacher_side, *, need_backward: bool = True,
@@ -959,16 +1012,12 @@ def procrustes_forward_cached(students: list[torch.Tensor], teacher_side, *, nee
     ``teacher_side``: a ``TeacherSide`` of tensors (copied into the call's slots), or what ``TeacherCache.load`` returns
     (gathered straight into them by one launch).  The token weights, the centring and the teacher Gram are not queued;
     everything from the student projection on is the uncached call's, through the same ``_ProcrustesPlan`` cache and
-    allocation scheme, so with the teacher side of an uncached call on the same students every output has that call's
+    call frame, so with the teacher side of an uncached call on the same students every output has that call's
     bits.  The returned context's ``teacher_side`` is the one the call read (views, as in ``procrustes_forward``)."""
     import ctypes
-    E = len(students)
-    students = [as_supported(s) for s in students]
-    students = _check_common_layout([s if s.stride(2) == 1 else s.contiguous() for s in students],
-                                    "student token tensors")
+    students, s_layout = _student_intake(students)
     _require_cuda(*students)
     s0 = students[0]
-    dev = s0.device
     B, n_s, d_s = s0.shape
     gather = getattr(teacher_side, "into", None)
     if gather is not None:
@@ -988,60 +1037,20 @@ def procrustes_forward_cached(students: list[torch.Tensor], teacher_side, *, nee
         if (teacher_side.g.dtype, teacher_side.omega.dtype, teacher_side.omega_t.dtype) != \
                 (torch.float64, torch.float32, torch.float32):
             raise TypeError("teacher side must be (fp64 g, fp32 omega, fp32 omega_t)")
-    need_bwd = need_backward or grad_layers is not None
-    want_dx = grad_layers is not None or uwso_ce is not None
     stream = _stream()
-    s_layout = (_dtype_code(s0), s0.stride(0), s0.stride(1), int(all(s.data_ptr() % 16 == 0 for s in students)))
-    # the teacher's own token grid and width do not matter any more: the core grid stands for the first (it decides
-    # the student-side taps exactly as n_t < n_s does), 1 for the second
-    key = ("given", E, B, n_s, d_s, n, need_bwd, want_sweeps, want_dx, uwso_ce is not None, dev, stream, TWO_PASS_SVD,
-           s_layout)
-    plan = _PROCRUSTES_PLANS.get(key)
-    if plan is None:
-        plan = _ProcrustesPlan(E, 1, B, n_s, d_s, n, 1, 1, n_s, False, need_bwd, False, want_sweeps, want_dx,
-                               uwso_ce is not None, s_layout, (0, 0, 0, 1), dev, given=True)
-        if len(_PROCRUSTES_PLANS) >= 8:
-            torch.cuda.synchronize(dev)
-            _PROCRUSTES_PLANS.clear()
-        _PROCRUSTES_PLANS[key] = plan
-    EB = E * B
-    kept = torch.empty((plan.kept_total,), device=dev, dtype=torch.float32)
-    omega, mu_s, a_prime, k_prime, terms, uw = (piece[:c] for piece, c in
-                                                zip(torch.split(kept, plan.kept_padded), plan.kept_sizes))
-    omega, mu_s = omega.view(1, B, n_s), mu_s.view(E, B, d_s)
-    a_prime = a_prime.view(E, B, n, d_s)
-    k_prime = k_prime.view(E, B, n, n) if need_bwd else None
-    terms = terms.view(4, E, B)
-    uw = uw if uwso_ce is not None else None
-    dx = torch.empty((E, B, n_s, d_s), device=dev, dtype=torch.float32) if want_dx else None
-    if plan.sweeps is not None:
-        plan.sweeps.zero_()
-    if uwso_ce is not None:
-        assert uwso_ce.dtype == torch.float32 and uwso_ce.numel() == 1 and uwso_ce.device == dev
-    if grad_layers is not None:
-        grad_layers = grad_layers.contiguous().float()
-    side = TeacherSide(plan.g_all[EB:EB + B], omega[0], plan.omega_t.view(B, n))
+    key = ("given", len(students), B, n_s, d_s, n, need_backward or grad_layers is not None, want_sweeps,
+           grad_layers is not None or uwso_ce is not None, uwso_ce is not None, s0.device, stream, TWO_PASS_SVD, s_layout)
+    plan = _cached_plan(key, lambda: _ProcrustesPlan.given(*key[1:]))
+    ctx = plan.begin(students, grad_layers, uwso_ce)
     if gather is not None:
-        gather(*side)
+        gather(*ctx.teacher_side)
     else:
-        for dst, src in zip(side, teacher_side):
+        for dst, src in zip(ctx.teacher_side, teacher_side):
             dst.copy_(src)
-
-    args = plan.args
-    for e, s in enumerate(students):
-        plan.host_ptrs[e] = s.data_ptr()
-    args.student_ptrs = _ptr_table(students).data_ptr()
-    args.omega, args.mu_s = omega.data_ptr(), mu_s.data_ptr()
-    args.tr_s, args.tr_t, args.nuc, args.loss_b = (terms[i].data_ptr() for i in range(4))
-    args.a_prime, args.k_prime = a_prime.data_ptr(), _ptr(k_prime)
-    args.dx, args.grad_layers = _ptr(dx), _ptr(grad_layers)
-    args.uw_ce, args.uw_out = _ptr(uwso_ce), _ptr(uw)
     gpu_mark("procrustes_begin")
-    _lib.call("basd_procrustes_forward_cached", ctypes.addressof(args), stream)
+    _lib.call("basd_procrustes_forward_cached", ctypes.addressof(plan.args), stream)
     gpu_mark("procrustes_end")
-    sweeps = plan.sweeps.clone() if plan.sweeps is not None else None
-    return ProcrustesContext(omega, mu_s, a_prime, k_prime, terms[0], terms[1], terms[2], terms[3], sweeps, None,
-                             dx, uw, side)
+    return plan.finish(ctx)
 
 
 def procrustes_teacher_side(teacher: torch.Tensor, attn: torch.Tensor, has_cls: bool, n_s: int, *,
@@ -1083,17 +1092,12 @@ def procrustes_teacher_side(teacher: torch.Tensor, attn: torch.Tensor, has_cls: 
     # scratch of this call alone, handed back to the allocator behind its launches on this stream
     mu_t, tc = torch.empty((B, d_t), **f32), torch.empty((B, n, d_t), **f32)
     slabs = torch.empty((g_splits * B, n, n), device=dev, dtype=torch.float64) if g_splits > 1 else None
-    tabs = _plan_taps(n_s, n_t, n_a, dev)
 
     a = _lib.ProcrustesArgs()
     a.L = a.G = 1
     a.B, a.n_s, a.n_t, a.d_t, a.H, a.A, a.has_cls, a.n_a, a.n = B, n_s, n_t, d_t, H, A, int(bool(has_cls)), n_a, n
-    a.tok_ptrs, a.attn_ptrs = _ptr_table([teacher]).data_ptr(), _ptr_table([attn]).data_ptr()
-    a.t_dtype, a.t_sb, a.t_sn, a.t_sd = (_dtype_code(teacher), *teacher.stride())
-    a.a_dtype = _dtype_code(attn)
-    a.a_sb, a.a_sh, a.a_sq, a.a_sk = attn.stride()
+    _set_teacher_args(a, [teacher], [attn], _plan_taps(n_s, n_t, n_a, dev))
     a.mix = _device_consts((1.0,), torch.float32, dev).data_ptr()
-    _set_taps(a, *tabs)
     a.omega, a.omega_t, a.mu_t, a.tc, a.g_all = (omega.data_ptr(), omega_t.data_ptr(), mu_t.data_ptr(), tc.data_ptr(),
                                                  g.data_ptr())
     a.g_splits, a.g_slabs = g_splits, _ptr(slabs)
@@ -1118,21 +1122,18 @@ def procrustes_student_grads(students: list[torch.Tensor], ctx: ProcrustesContex
     _, B, n, d_s = ctx.a_prime.shape
     dev = ctx.a_prime.device
     n_s = students[0].shape[1]
-    tp = taps(n, n_s, dev)
-    t0, t1, lam = (tp.tap0.data_ptr(), tp.tap1.data_ptr(), tp.lam.data_ptr()) if tp else (None, None, None)
+    t0, t1, lam = _tap_ptrs(taps(n, n_s, dev))
     st = _stream()
     grad_layers = grad_layers.contiguous().float()
-    xs = [as_supported(x) for x in students]
-    xs = _check_common_layout([x if x.stride(2) == 1 else x.contiguous() for x in xs], "student token tensors")
+    xs, (x_dtype, x_sb, x_sn, x_aligned) = _student_intake(students)
     dx = torch.empty((E, B, n_s, d_s), device=dev, dtype=torch.float32)
     shared = ctx.omega.shape[0] == 1
     if tnorm2 is None and n <= 64:
         # small cores: H = K' A' formed inside the gradient kernel (never stored)
         status = getattr(_lib.load(), "basd_student_grad_fused")(
-            _ptr_table(xs).data_ptr(), _dtype_code(xs[0]), xs[0].stride(0), xs[0].stride(1), E, B, n_s, n, d_s,
-            int(all(x.data_ptr() % 16 == 0 for x in xs)), ctx.omega.data_ptr(), 0 if shared else B * n_s,
-            ctx.mu_s.data_ptr(), ctx.k_prime.data_ptr(), ctx.a_prime.data_ptr(), t0, t1, lam, grad_layers.data_ptr(),
-            2.0 / B, dx.data_ptr(), st)
+            _ptr_table(xs).data_ptr(), x_dtype, x_sb, x_sn, E, B, n_s, n, d_s, x_aligned, ctx.omega.data_ptr(),
+            0 if shared else B * n_s, ctx.mu_s.data_ptr(), ctx.k_prime.data_ptr(), ctx.a_prime.data_ptr(), t0, t1, lam,
+            grad_layers.data_ptr(), 2.0 / B, dx.data_ptr(), st)
         if status == 0:
             return list(dx.unbind(0))
         if status != _lib.EUNSUPPORTED:
@@ -1143,9 +1144,9 @@ def procrustes_student_grads(students: list[torch.Tensor], ctx: ProcrustesContex
     h = gemm_tn(kp[0], ap[0], batch=E * B, a_batch_stride=n * n, b_batch_stride=n * d_s, krows=n, m_cols=n,
                 n_cols=d_s, split=False).view(E, B, n, d_s)
     gomega = torch.empty((E, B, n_s), device=dev, dtype=torch.float32) if tnorm2 is not None else None
-    _lib.call("basd_student_grad_multi", _ptr_table(xs).data_ptr(), _dtype_code(xs[0]), xs[0].stride(0),
-              xs[0].stride(1), E, B, n_s, n, d_s, ctx.omega.data_ptr(), 0 if shared else B * n_s, ctx.mu_s.data_ptr(),
-              h.data_ptr(), t0, t1, lam, grad_layers.data_ptr(), 2.0 / B, dx.data_ptr(), _ptr(tnorm2), _ptr(gomega), st)
+    _lib.call("basd_student_grad_multi", _ptr_table(xs).data_ptr(), x_dtype, x_sb, x_sn, E, B, n_s, n, d_s,
+              ctx.omega.data_ptr(), 0 if shared else B * n_s, ctx.mu_s.data_ptr(), h.data_ptr(), t0, t1, lam,
+              grad_layers.data_ptr(), 2.0 / B, dx.data_ptr(), _ptr(tnorm2), _ptr(gomega), st)
     grads = list(dx.unbind(0))
     return (grads, gomega) if tnorm2 is not None else grads
 
@@ -1156,14 +1157,11 @@ def procrustes_teacher_factor(ctx: ProcrustesContext) -> tuple[torch.Tensor, tor
     E, B = ctx.loss_b.shape
     n, n_s = mg["n"], mg["n_s"]
     dev = ctx.loss_b.device
-    tp = mg["student_taps"]
-    t0, t1, lam = (tp.tap0.data_ptr(), tp.tap1.data_ptr(), tp.lam.data_ptr()) if tp else (None, None, None)
-    r0, r1 = (tp.range0.data_ptr(), tp.range1.data_ptr()) if tp else (None, None)
     kt = torch.empty((E * B, n, n), device=dev, dtype=torch.float32)
     tnorm2 = torch.empty((E, B, n_s), device=dev, dtype=torch.float32)
     common = (mg["W"].data_ptr(), 2 * n * n, mg["sigma"].data_ptr(), n, n_s, E * B, mg["l_a"].data_ptr(),
-              mg["g_b"].data_ptr(), n * n, mg["omega_e"].data_ptr(), t0, t1, lam, r0, r1, kt.data_ptr(),
-              tnorm2.data_ptr())
+              mg["g_b"].data_ptr(), n * n, mg["omega_e"].data_ptr(), *_tap_ptrs(mg["student_taps"], ranges=True),
+              kt.data_ptr(), tnorm2.data_ptr())
     # the tiled form (Z through scratch) for every order: 0.87 ms against 7.5 for the LDS-resident kernel at 512 cores of
     # 196 tokens, 0.04 against 0.19 at 64 tokens (tools/probe/teacher_factor_ab.py)
     scratch = torch.empty((E * B, n, n), device=dev, dtype=torch.float32)
@@ -1189,8 +1187,7 @@ def procrustes_mix_grads(ctx: ProcrustesContext, kt: torch.Tensor, gomega: torch
     # R = Kt T_c per (layer, sample); Kt is symmetric, so the TN contraction applies
     r = gemm_tn(kt[0], tc[0], batch=E * B, a_batch_stride=n * n, b_batch_stride=n * d_t, krows=n, m_cols=n,
                 n_cols=d_t, split=False)
-    gt = mg["gather"]
-    g0, g1, glam = (gt.tap0.data_ptr(), gt.tap1.data_ptr(), gt.lam.data_ptr()) if gt else (None, None, None)
+    g0, g1, glam = _tap_ptrs(mg["gather"])
     part_tok = torch.empty((E, B, L), device=dev, dtype=torch.float32)
     tsb, tsn, tsd = teachers[0].stride()
     if E <= 4 and L > 1:
@@ -1202,16 +1199,13 @@ def procrustes_mix_grads(ctx: ProcrustesContext, kt: torch.Tensor, gomega: torch
     else:
         _lib.call("basd_mix_grad_tokens", r.data_ptr(), mg["tok_tab"].data_ptr(), _dtype_code(teachers[0]), L, tsb,
                   tsn, tsd, E, B, n, d_t, g0, g1, glam, part_tok.data_ptr(), st)
-    atp = mg["attn_taps"]
-    a0, a1, alam = (atp.tap0.data_ptr(), atp.tap1.data_ptr(), atp.lam.data_ptr()) if atp else (None, None, None)
-    ar0, ar1 = (atp.range0.data_ptr(), atp.range1.data_ptr()) if atp else (None, None)
     sb, sh, sq, sk = attns[0].stride()
     H, A = attns[0].shape[1], attns[0].shape[2]
     part_att = torch.empty((E, B, L), device=dev, dtype=torch.float32)
     g_raw = torch.empty((E, B, n_a), device=dev, dtype=torch.float32) if want_inputs else None
-    _lib.call("basd_token_weight_bwd", gomega.data_ptr(), mg["raw"].data_ptr(), E, B, n_a, n_s, a0, a1, alam, ar0,
-              ar1, mg["att_tab"].data_ptr(), _dtype_code(attns[0]), L, sb, sh, sq, sk, H, A, int(mg["has_cls"]),
-              part_att.data_ptr(), _ptr(g_raw), st)
+    _lib.call("basd_token_weight_bwd", gomega.data_ptr(), mg["raw"].data_ptr(), E, B, n_a, n_s,
+              *_tap_ptrs(mg["attn_taps"], ranges=True), mg["att_tab"].data_ptr(), _dtype_code(attns[0]), L, sb, sh, sq,
+              sk, H, A, int(mg["has_cls"]), part_att.data_ptr(), _ptr(g_raw), st)
     per_layer = (2.0 * part_tok + part_att).sum(dim=1) / B                 # (E, L): tiny torch glue
     g_mix = per_layer * grad_layers.float().view(E, 1)
     return (g_mix, r, g_raw) if want_inputs else g_mix
